@@ -23,6 +23,12 @@ scatter protocol is implemented and gloo-tested but serializes at DP=8).
 Launch (the driver's contract):
   python bench.py --gpus N --steps K --warmup W
   torchrun --nnodes=1 --nproc-per-node N bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints one JSON line.
+``--full`` (1 GPU) additionally runs the secondary measurements (ILQL bf16 and
+a gpt2-xl model-ladder entry) and carries them in that line's ``secondary``.
+``--dump-outputs DIR`` writes what the last timed step computed as
+``DIR/<name>.npy`` so two builds can be compared output for output.
 """
 
 import argparse
@@ -146,8 +152,14 @@ def parse_args(argv=None):
     p.add_argument("--method", choices=["ppo", "ilql"], default="ppo")
     p.add_argument("--tiny-smoke", action="store_true",
                    help="tiny model for the torchrun CPU contract dry-run (not a benchmark)")
+    p.add_argument("--full", action="store_true",
+                   help="after the flagship measurement also run the secondary ILQL / "
+                        "model-ladder measurements (1 GPU) and carry them in the result line")
     p.add_argument("--no-secondary", action="store_true",
-                   help="skip the secondary ILQL / model-ladder measurements")
+                   help="with --full: skip the secondary ILQL / model-ladder measurements")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last timed step computed "
+                        "(rollouts + a seeded sample of the trained weights) as DIR/<name>.npy")
     return p.parse_args(argv)
 
 
@@ -239,10 +251,13 @@ def main():
     else:
         result = None
 
-    # secondary measurements (1-GPU only): BASELINE config #2 (ILQL bf16) and
-    # a model-ladder entry, carried inside the single JSON line so the driver
-    # records more than the flagship number
-    if world == 1 and not args.no_secondary and not args.tiny_smoke:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ppo_outputs(trainer))
+
+    # secondary measurements (--full, 1-GPU only): BASELINE config #2 (ILQL
+    # bf16) and a model-ladder entry, carried inside the single JSON line so
+    # the driver records more than the flagship number
+    if args.full and world == 1 and not args.no_secondary and not args.tiny_smoke:
         del trainer
         if torch.cuda.is_available():
             torch.cuda.empty_cache()
@@ -262,6 +277,51 @@ def main():
 
     if result is not None:
         print(json.dumps(result))
+
+
+DUMP_PARAM_SAMPLE = 65536  # elements kept per trained tensor (seeded sample)
+DUMP_PARAM_BUDGET = 8 * 2**20  # elements kept over all trained tensors (32 MB fp32)
+
+
+def trained_param_sample(model):
+    """A fixed, seeded sample of every trainable parameter, concatenated in
+    parameters() order: the weights the timed steps updated."""
+    import numpy as np
+
+    rng = np.random.RandomState(0)
+    trained = [p for p in model.parameters() if p.requires_grad]
+    # whole dump stays far below 64 MB however many tensors are trainable
+    keep = min(DUMP_PARAM_SAMPLE, DUMP_PARAM_BUDGET // max(len(trained), 1))
+    parts = []
+    for p in trained:
+        flat = p.detach().reshape(-1)
+        if flat.numel() > keep:
+            idx = np.sort(rng.choice(flat.numel(), keep, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        parts.append(flat.float().cpu())
+    return torch.cat(parts) if parts else torch.zeros(0)
+
+
+def ppo_outputs(trainer):
+    """What the last PPO cycle left for its caller: the rollouts it collected
+    (padded to the widest row, store order) and the weights it trained."""
+    loader = trainer.store.create_loader(len(trainer.store), shuffle=False)
+    batch = next(iter(loader))
+    out = {k: getattr(batch, k) for k in
+           ("query_tensors", "response_tensors", "logprobs", "values", "rewards")}
+    out["trained_params"] = trained_param_sample(trainer.model)
+    return out
+
+
+def dump_outputs(out_dir, arrays):
+    """Write each array as ``out_dir/<name>.npy`` in float32 (token ids are
+    below 2**24, so they survive the cast exactly)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"),
+                t.detach().to(device="cpu", dtype=torch.float32).numpy())
 
 
 def _clone_args(args, **over):
@@ -363,6 +423,8 @@ def run_ilql(args, emit=True):
         torch.distributed.all_reduce(t, torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
     total = config.train.batch_size * args.steps * 4 * world
+    if emit and args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"trained_params": trained_param_sample(trainer.model)})
     result = None
     if rank == 0:
         result = {

@@ -20,5 +20,5 @@ python examples/randomwalks/ppo_randomwalks.py \
   "$(echo $CONF_RW | python -c 'import json,sys; d=json.load(sys.stdin); d["train.logging_dir"]="'"$OUT"'/ppo_randomwalks"; d["method.num_rollouts"]=32; d["method.chunk_size"]=32; print(json.dumps(d))')"
 
 echo "[benchmark] flagship GPT-2 PPO samples/sec"
-python bench.py --steps 2 --warmup 1 > "$OUT/bench_gpt2_ppo.json"
+python bench.py --steps 2 --warmup 1 --full > "$OUT/bench_gpt2_ppo.json"
 cat "$OUT/bench_gpt2_ppo.json"

@@ -61,3 +61,37 @@ def test_bench_single_process_contract():
     assert out.returncode == 0, out.stderr[-4000:]
     result = _last_json_line(out.stdout)
     assert result["n_gpus"] == 1 and result["value"] > 0
+
+
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """--dump-outputs writes the last timed step's rollouts and trained
+    weights as float32 .npy files, and two runs with the same arguments start
+    from identical inputs (on CPU the whole step is deterministic, so every
+    dumped array must match exactly)."""
+    import numpy as np
+
+    env = dict(os.environ)
+    env["HIP_VISIBLE_DEVICES"] = ""
+    env["CUDA_VISIBLE_DEVICES"] = ""
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    names = ("query_tensors", "response_tensors", "logprobs", "values", "rewards",
+             "trained_params")
+    dumps = []
+    for run in ("a", "b"):
+        out_dir = tmp_path / run
+        cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "2",
+               "--warmup", "0", *TINY, "--dump-outputs", str(out_dir)]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=REPO, env=env)
+        assert out.returncode == 0, out.stderr[-4000:]
+        result = _last_json_line(out.stdout)
+        assert result["steps"] == 2 and result["ms_per_step"] > 0
+        assert "secondary" not in result
+        assert sorted(os.listdir(out_dir)) == sorted(f"{n}.npy" for n in names)
+        dumps.append({n: np.load(out_dir / f"{n}.npy") for n in names})
+    for n in names:
+        a, b = dumps[0][n], dumps[1][n]
+        assert a.dtype == np.float32 and a.size > 0
+        assert np.isfinite(a).all()
+        assert a.shape == b.shape and np.array_equal(a, b), n
+    assert dumps[0]["query_tensors"].shape[0] == 8  # --num-rollouts rows

@@ -3,6 +3,7 @@ gradient reducer, and distributed statistics — the CPU stand-ins for the
 RCCL/xGMI paths exercised on the GPU node."""
 
 import os
+import tempfile
 
 import pytest
 import torch
@@ -10,6 +11,12 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 WORLD = 2
+
+
+def _scratch(name):
+    """Per-user scratch directory (every rank computes the same path): a fixed
+    name under the temp dir breaks once another user has left one behind."""
+    return os.path.join(tempfile.gettempdir(), f"trlx_amd_tests_{os.getuid()}", name)
 
 
 def _run(rank, fn, port):
@@ -174,7 +181,7 @@ def _worker_ppo_train(rank):
     cfg.train.checkpoint_interval = 100
     cfg.train.tracker = None
     cfg.train.save_best = False
-    cfg.train.checkpoint_dir = f"/tmp/dist_ppo_{rank}"
+    cfg.train.checkpoint_dir = _scratch(f"dist_ppo_{rank}")
     cfg.method.num_rollouts = 4
     cfg.method.chunk_size = 2
     cfg.method.ppo_epochs = 1
@@ -323,7 +330,7 @@ def _worker_tp_ppo(rank):
         cfg.train.tracker = None
         cfg.train.save_best = False
         cfg.train.tensor_parallel_size = 2
-        cfg.train.checkpoint_dir = f"/tmp/tp_ppo_{rank}"
+        cfg.train.checkpoint_dir = _scratch(f"tp_ppo_{rank}")
         cfg.method.num_rollouts = 4
         cfg.method.chunk_size = 2
         cfg.method.ppo_epochs = 1
@@ -513,7 +520,7 @@ def _worker_tp_checkpoint(rank):
     full = CausalTransformer(cfg)
     full_sd = {k: v for k, v in full.state_dict().items() if not k.startswith("rope_")}
 
-    out_dir = "/tmp/tp_ckpt_test"
+    out_dir = _scratch("tp_ckpt_test")
     topo.init_model_parallel(tp_size=WORLD)
     try:
         sharded = CausalTransformer(cfg)
@@ -690,7 +697,7 @@ def _worker_pp_hydra_model(rank):
         assert torch.equal(samples_pp, samples_full), (samples_pp, samples_full)
 
         # sharded checkpoint round-trip through the PP merge
-        out_dir = f"/tmp/pp_ckpt_test"
+        out_dir = _scratch("pp_ckpt_test")
         model.save_pretrained(out_dir)
         dist.barrier()
         if rank == 0:
@@ -739,7 +746,7 @@ def _ppo_cfg_for_pp(rank, pp, tp=1, arch="gpt2"):
     cfg.train.save_best = False
     cfg.train.pipeline_parallel_size = pp
     cfg.train.tensor_parallel_size = tp
-    cfg.train.checkpoint_dir = f"/tmp/dist_ppo_pp_{rank}"
+    cfg.train.checkpoint_dir = _scratch(f"dist_ppo_pp_{rank}")
     cfg.method.num_rollouts = 4
     cfg.method.chunk_size = 2
     cfg.method.ppo_epochs = 1
@@ -865,7 +872,7 @@ def _worker_pp_sft_train(rank):
     cfg.train.tracker = None
     cfg.train.save_best = False
     cfg.train.pipeline_parallel_size = 2
-    cfg.train.checkpoint_dir = f"/tmp/dist_sft_pp_{rank}"
+    cfg.train.checkpoint_dir = _scratch(f"dist_sft_pp_{rank}")
     cfg.method.gen_kwargs = dict(max_new_tokens=4, top_k=0, top_p=1.0, do_sample=True)
 
     try:
@@ -913,7 +920,7 @@ def _worker_cross_tp_reshard(rank):
                             arch_name="gpt2", tie_word_embeddings=False)
     full = CausalTransformer(cfg)
     full_sd = {k: v for k, v in full.state_dict().items() if not k.startswith("rope_")}
-    out_dir = "/tmp/cross_tp_ckpt_test"
+    out_dir = _scratch("cross_tp_ckpt_test")
 
     topo.reset()
     try:
@@ -989,7 +996,7 @@ def _worker_pp_ilql_train(rank):
     cfg.train.tracker = None
     cfg.train.save_best = False
     cfg.train.pipeline_parallel_size = 2
-    cfg.train.checkpoint_dir = f"/tmp/dist_ilql_pp_{rank}"
+    cfg.train.checkpoint_dir = _scratch(f"dist_ilql_pp_{rank}")
     cfg.method.gen_kwargs = dict(max_new_tokens=4, top_k=5, beta=1, temperature=1.0)
 
     try:
@@ -1033,7 +1040,7 @@ def _worker_ppo_local_rewards(rank):
     cfg.train.checkpoint_interval = 100
     cfg.train.tracker = None
     cfg.train.save_best = False
-    cfg.train.checkpoint_dir = f"/tmp/dist_ppo_lr_{rank}"
+    cfg.train.checkpoint_dir = _scratch(f"dist_ppo_lr_{rank}")
     cfg.method.num_rollouts = 4
     cfg.method.chunk_size = 2
     cfg.method.ppo_epochs = 1

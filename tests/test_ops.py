@@ -320,6 +320,31 @@ def test_gpu_gae_and_whiten():
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("n", [1, 255, 1280, 256 * 2048 + 77])
+def test_gpu_whiten_stats_repeatable(n):
+    """The whitening statistics must not depend on block scheduling: the same
+    input gives bit-identical [sum, sumsq, count] on every call (one block,
+    a partial block, the PPO minibatch size 32x40 = 5 blocks, and past the
+    2048-block grid cap where the grid-stride loop runs more than once).
+    Accuracy bound: any-order fp32 summation of n terms errs by at most
+    (n-1) * 2^-24 * sum|x| (Higham, Accuracy and Stability, eq. 4.4)."""
+    import trlx_amd._C as ext
+
+    torch.manual_seed(41)
+    xs = (torch.randn(n) * 2 + 3).cuda()
+    first = ext.sum_count(xs)
+    for _ in range(20):
+        assert torch.equal(ext.sum_count(xs), first)
+    x64 = xs.double().cpu()
+    u = 2.0 ** -24
+    got = first.double().cpu()
+    assert abs(got[0] - x64.sum()) <= max(n - 1, 1) * u * x64.abs().sum()
+    # x*x rounds once more per term before the summation
+    assert abs(got[1] - (x64 * x64).sum()) <= (max(n - 1, 1) + 1) * u * (x64 * x64).sum()
+    assert got[2] == n
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_gpu_causal_softmax(dtype):
     torch.manual_seed(5)

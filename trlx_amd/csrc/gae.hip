@@ -68,7 +68,12 @@ __global__ void gae_kernel(const float* __restrict__ values, const float* __rest
 }
 
 // sum + sum-of-squares for whitening; the exact count is set host-side.
-__global__ void sum_sq_kernel(const float* __restrict__ x, float* __restrict__ stats, long n) {
+// Two phases with plain stores: every block writes its partial pair, then one
+// block adds the partials in a fixed order.  (Float atomicAdd into stats made
+// the result depend on block arrival order: the same input whitened to
+// ulp-different advantages from call to call, which Adam then amplifies.)
+__global__ void sum_sq_partial_kernel(const float* __restrict__ x, float* __restrict__ partials,
+                                      long n) {
   __shared__ float rbuf[4];
   float s = 0.f, ss = 0.f;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
@@ -79,8 +84,26 @@ __global__ void sum_sq_kernel(const float* __restrict__ x, float* __restrict__ s
   s = block_sum<4>(s, rbuf);
   ss = block_sum<4>(ss, rbuf);
   if (threadIdx.x == 0) {
-    atomicAdd(&stats[0], s);
-    atomicAdd(&stats[1], ss);
+    partials[2 * blockIdx.x] = s;
+    partials[2 * blockIdx.x + 1] = ss;
+  }
+}
+
+// one block of 256 threads: strided read of the nblocks partial pairs, then a
+// fixed-shape block reduction; writes stats[0] (sum) and stats[1] (sumsq)
+__global__ void sum_sq_final_kernel(const float* __restrict__ partials, float* __restrict__ stats,
+                                    int nblocks) {
+  __shared__ float rbuf[4];
+  float s = 0.f, ss = 0.f;
+  for (int i = threadIdx.x; i < nblocks; i += blockDim.x) {
+    s += partials[2 * i];
+    ss += partials[2 * i + 1];
+  }
+  s = block_sum<4>(s, rbuf);
+  ss = block_sum<4>(ss, rbuf);
+  if (threadIdx.x == 0) {
+    stats[0] = s;
+    stats[1] = ss;
   }
 }
 
@@ -127,7 +150,12 @@ at::Tensor sum_count(const at::Tensor& x) {
   constexpr int BLOCK = 256;
   const int grid = (int)std::min<long>((n + BLOCK - 1) / BLOCK, 2048);
   auto stream = c10::hip::getCurrentHIPStream();
-  sum_sq_kernel<<<grid, BLOCK, 0, stream>>>(x.data_ptr<float>(), stats.data_ptr<float>(), n);
+  auto partials = at::empty({2L * grid}, x.options());
+  sum_sq_partial_kernel<<<grid, BLOCK, 0, stream>>>(x.data_ptr<float>(),
+                                                    partials.data_ptr<float>(), n);
+  HIP_CHECK_LAST();
+  sum_sq_final_kernel<<<1, BLOCK, 0, stream>>>(partials.data_ptr<float>(),
+                                               stats.data_ptr<float>(), grid);
   HIP_CHECK_LAST();
   return stats;
 }

@@ -83,6 +83,15 @@ class PipelineStage(nn.Module):
             self.register_buffer("rope_sin", sin, persistent=False)
         else:
             self.rope_cos = self.rope_sin = None
+        # the TP linears allocate their shards with torch.empty and leave the
+        # fill to the owning model (CausalTransformer._init_weights); a stage
+        # built from a bare config has no such pass, so fill them here or the
+        # first forward reads uninitialized memory (NaN logits under TP x PP)
+        from .tp import ColumnParallelLinear, RowParallelLinear
+
+        for m in self.modules():
+            if isinstance(m, (ColumnParallelLinear, RowParallelLinear)):
+                m.weight.data.normal_(mean=0.0, std=0.02)
 
     @property
     def rope_tables(self):
