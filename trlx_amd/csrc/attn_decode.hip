@@ -16,11 +16,14 @@ namespace {
 constexpr int BLOCK = 256;
 constexpr int NWAVES = BLOCK / WAVE;
 
-template <int D>
+// ALIBI is a template parameter in both kernels (not a runtime null test):
+// the no-bias instantiations compile to exactly the code they were without it.
+template <int D, bool ALIBI>
 __global__ void attn_decode_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ kc,
                                    const bf16_t* __restrict__ vc, const int* __restrict__ seq_lens,
-                                   const int* __restrict__ seq_starts, bf16_t* __restrict__ out,
-                                   int Hq, int Hkv, int S, float scale) {
+                                   const int* __restrict__ seq_starts,
+                                   const float* __restrict__ alibi_slopes /* [Hq], iff ALIBI */,
+                                   bf16_t* __restrict__ out, int Hq, int Hkv, int S, float scale) {
   constexpr int G = D / 8;          // lanes cooperating on one key
   constexpr int KPW = WAVE / G;     // keys per wave per iteration
   constexpr int NPART = NWAVES * KPW;  // independent (m, s, o) partials
@@ -30,6 +33,7 @@ __global__ void attn_decode_kernel(const bf16_t* __restrict__ q, const bf16_t* _
   const int hkv = hq / (Hq / Hkv);
   const int len = seq_lens[b];
   const int kstart = seq_starts ? seq_starts[b] : 0;
+  const float slope = ALIBI ? alibi_slopes[hq] : 0.f;  // QUERY head, not hkv
 
   const int lane = threadIdx.x % WAVE;
   const int wid = threadIdx.x / WAVE;
@@ -63,7 +67,7 @@ __global__ void attn_decode_kernel(const bf16_t* __restrict__ q, const bf16_t* _
       // reduce across the G lanes of this key group (contiguous lanes)
 #pragma unroll
       for (int off = G / 2; off > 0; off >>= 1) partial += __shfl_xor(partial, off);
-      const float score = partial;
+      const float score = ALIBI ? alibi_score(partial, slope, key, kstart) : partial;
       // branchless online update (first valid key: m=-inf -> corr=0)
       const float mnew = fmaxf(m, score);
       const float corr = (m > -INFINITY) ? __expf(m - mnew) : 0.f;
@@ -113,7 +117,7 @@ __global__ void attn_decode_kernel(const bf16_t* __restrict__ q, const bf16_t* _
 // launch and the [B, Hq, 1, D] q round-trip through HBM disappear.  The
 // freshly appended key/value at cache position *cache_idx are read back
 // through the same CU's L1 after __syncthreads() (intra-block global RAW).
-template <int D, bool INTERLEAVED>
+template <int D, bool INTERLEAVED, bool ALIBI>
 __global__ void fused_decode_attn_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ kc,
                                          bf16_t* __restrict__ vc,
                                          const int* __restrict__ seq_lens,
@@ -121,6 +125,8 @@ __global__ void fused_decode_attn_kernel(const bf16_t* __restrict__ qkv, bf16_t*
                                          const float* __restrict__ cs,
                                          const float* __restrict__ sn,
                                          const long* __restrict__ cache_idx,
+                                         // [H], read iff ALIBI (host: never with cs/sn)
+                                         const float* __restrict__ alibi_slopes,
                                          bf16_t* __restrict__ out, int H, int S, int rot,
                                          float scale) {
   constexpr int G = D / 8;
@@ -131,6 +137,7 @@ __global__ void fused_decode_attn_kernel(const bf16_t* __restrict__ qkv, bf16_t*
   const int h = blockIdx.x % H;
   const int len = seq_lens[b];
   const int kstart = seq_starts ? seq_starts[b] : 0;
+  const float slope = ALIBI ? alibi_slopes[h] : 0.f;
   const long pos = *cache_idx;
 
   const int lane = threadIdx.x % WAVE;
@@ -166,7 +173,7 @@ __global__ void fused_decode_attn_kernel(const bf16_t* __restrict__ qkv, bf16_t*
         if (wid == 0) q_lds[i] = bf2f(src[i].u) * scale;
         else kdst[i] = src[i];
       }
-    } else if (wid < 2) {  // no rope (learned/alibi-free path)
+    } else if (wid < 2) {  // no rope (learned positions, or ALiBi: bias added in stage 2)
       for (int i = lane; i < D; i += WAVE) {
         if (wid == 0) q_lds[i] = bf2f(src[i].u) * scale;
         else kdst[i] = src[i];
@@ -203,7 +210,7 @@ __global__ void fused_decode_attn_kernel(const bf16_t* __restrict__ qkv, bf16_t*
       for (int i = 0; i < 8; ++i) partial += qf[i] * kf[i];
 #pragma unroll
       for (int off = G / 2; off > 0; off >>= 1) partial += __shfl_xor(partial, off);
-      const float score = partial;
+      const float score = ALIBI ? alibi_score(partial, slope, key, kstart) : partial;
       const float mnew = fmaxf(m, score);
       const float corr = (m > -INFINITY) ? __expf(m - mnew) : 0.f;
       const float pw = __expf(score - mnew);
@@ -251,13 +258,17 @@ at::Tensor fused_decode_attention(const at::Tensor& qkv, at::Tensor& kcache, at:
                                   const c10::optional<at::Tensor>& cos,
                                   const c10::optional<at::Tensor>& sin,
                                   const at::Tensor& cache_idx, long rot, bool interleaved,
-                                  double scale) {
+                                  double scale,
+                                  const c10::optional<at::Tensor>& alibi_slopes) {
   TORCH_CHECK(qkv.is_cuda() && qkv.dtype() == at::kBFloat16 && qkv.is_contiguous());
   const int B = qkv.size(0);
   const int Hkv = kcache.size(1), S = kcache.size(2), D = kcache.size(3);
   const int QKV = qkv.numel() / B;
   TORCH_CHECK(QKV == 3 * Hkv * D, "fused_decode_attention requires Hq == Hkv");
   TORCH_CHECK(seq_lens.dtype() == at::kInt && seq_lens.numel() == B);
+  TORCH_CHECK(!(alibi_slopes.has_value() && cos.has_value()),
+              "fused_decode_attention: alibi_slopes and RoPE cos/sin are mutually exclusive");
+  const float* asl = alibi_slopes_ptr(alibi_slopes, qkv, Hkv, "fused_decode_attention");
   auto out = at::empty({B, Hkv, 1, D}, qkv.options());
   if (B == 0) return out;
   const float* cs = nullptr;
@@ -281,7 +292,18 @@ at::Tensor fused_decode_attention(const at::Tensor& qkv, at::Tensor& kcache, at:
   auto op = reinterpret_cast<bf16_t*>(out.data_ptr());
   auto sl = seq_lens.data_ptr<int>();
   auto ci = cache_idx.data_ptr<long>();
-#define LAUNCH_FUSED(DV)                                                                         do {                                                                                             if (interleaved)                                                                                 fused_decode_attn_kernel<DV, true><<<grid, BLOCK, 0, stream>>>(                                    qp, kp, vp, sl, ss, cs, sn, ci, op, Hkv, S, (int)rot, (float)scale);                     else                                                                                             fused_decode_attn_kernel<DV, false><<<grid, BLOCK, 0, stream>>>(                                   qp, kp, vp, sl, ss, cs, sn, ci, op, Hkv, S, (int)rot, (float)scale);                   } while (0)
+#define LAUNCH_FUSED(DV)                                                           \
+  do {                                                                             \
+    if (asl != nullptr) /* no RoPE on this branch (checked above) */               \
+      fused_decode_attn_kernel<DV, false, true><<<grid, BLOCK, 0, stream>>>(       \
+          qp, kp, vp, sl, ss, cs, sn, ci, asl, op, Hkv, S, (int)rot, (float)scale); \
+    else if (interleaved)                                                          \
+      fused_decode_attn_kernel<DV, true, false><<<grid, BLOCK, 0, stream>>>(       \
+          qp, kp, vp, sl, ss, cs, sn, ci, asl, op, Hkv, S, (int)rot, (float)scale); \
+    else                                                                           \
+      fused_decode_attn_kernel<DV, false, false><<<grid, BLOCK, 0, stream>>>(      \
+          qp, kp, vp, sl, ss, cs, sn, ci, asl, op, Hkv, S, (int)rot, (float)scale); \
+  } while (0)
   switch (D) {
     case 32: LAUNCH_FUSED(32); break;
     case 64: LAUNCH_FUSED(64); break;
@@ -296,7 +318,8 @@ at::Tensor fused_decode_attention(const at::Tensor& qkv, at::Tensor& kcache, at:
 
 at::Tensor attention_decode(const at::Tensor& q, const at::Tensor& kc, const at::Tensor& vc,
                             const at::Tensor& seq_lens, double scale,
-                            const c10::optional<at::Tensor>& seq_starts) {
+                            const c10::optional<at::Tensor>& seq_starts,
+                            const c10::optional<at::Tensor>& alibi_slopes) {
   TORCH_CHECK(q.is_cuda() && q.dtype() == at::kBFloat16 && q.is_contiguous());
   TORCH_CHECK(kc.is_contiguous() && vc.is_contiguous());
   TORCH_CHECK(q.dim() == 4 && q.size(2) == 1, "attention_decode: q must be [B,Hq,1,D]");
@@ -304,6 +327,7 @@ at::Tensor attention_decode(const at::Tensor& q, const at::Tensor& kc, const at:
   const int Hkv = kc.size(1), S = kc.size(2);
   TORCH_CHECK(kc.size(3) == D && Hq % Hkv == 0);
   TORCH_CHECK(seq_lens.dtype() == at::kInt && seq_lens.numel() == B);
+  const float* asl = alibi_slopes_ptr(alibi_slopes, q, Hq, "attention_decode");
   auto out = at::empty_like(q);
   if (B == 0) return out;
   auto stream = c10::hip::getCurrentHIPStream();
@@ -320,22 +344,24 @@ at::Tensor attention_decode(const at::Tensor& q, const at::Tensor& kc, const at:
     TORCH_CHECK(ssc.numel() == B && ssc.dtype() == at::kInt);
     ss = ssc.data_ptr<int>();
   }
+#define LAUNCH_DECODE(DV)                                                                  \
+  do {                                                                                     \
+    if (asl != nullptr)                                                                    \
+      attn_decode_kernel<DV, true><<<grid, BLOCK, 0, stream>>>(qp, kp, vp, sl, ss, asl, op, \
+                                                               Hq, Hkv, S, (float)scale);  \
+    else                                                                                   \
+      attn_decode_kernel<DV, false><<<grid, BLOCK, 0, stream>>>(qp, kp, vp, sl, ss, asl, op, \
+                                                                Hq, Hkv, S, (float)scale); \
+  } while (0)
   switch (D) {
-    case 32:
-      attn_decode_kernel<32><<<grid, BLOCK, 0, stream>>>(qp, kp, vp, sl, ss, op, Hq, Hkv, S, (float)scale);
-      break;
-    case 64:
-      attn_decode_kernel<64><<<grid, BLOCK, 0, stream>>>(qp, kp, vp, sl, ss, op, Hq, Hkv, S, (float)scale);
-      break;
-    case 128:
-      attn_decode_kernel<128><<<grid, BLOCK, 0, stream>>>(qp, kp, vp, sl, ss, op, Hq, Hkv, S, (float)scale);
-      break;
-    case 256:
-      attn_decode_kernel<256><<<grid, BLOCK, 0, stream>>>(qp, kp, vp, sl, ss, op, Hq, Hkv, S, (float)scale);
-      break;
+    case 32: LAUNCH_DECODE(32); break;
+    case 64: LAUNCH_DECODE(64); break;
+    case 128: LAUNCH_DECODE(128); break;
+    case 256: LAUNCH_DECODE(256); break;
     default:
       TORCH_CHECK(false, "attention_decode: head dim must be 32/64/128/256, got ", D);
   }
+#undef LAUNCH_DECODE
   HIP_CHECK_LAST();
   return out;
 }

@@ -46,7 +46,8 @@ at::Tensor causal_softmax_fwd(const at::Tensor& scores, long start_pos,
 at::Tensor causal_softmax_bwd(const at::Tensor& probs, const at::Tensor& dprobs);
 at::Tensor attention_decode(const at::Tensor& q, const at::Tensor& kc, const at::Tensor& vc,
                             const at::Tensor& seq_lens, double scale,
-                            const c10::optional<at::Tensor>& seq_starts);
+                            const c10::optional<at::Tensor>& seq_starts,
+                            const c10::optional<at::Tensor>& alibi_slopes);
 at::Tensor lm_logprobs_v2(const at::Tensor& hidden, const at::Tensor& weight,
                           const at::Tensor& labels);
 at::Tensor skinny_gemm(const at::Tensor& a, const at::Tensor& w,
@@ -64,7 +65,8 @@ at::Tensor fused_decode_attention(const at::Tensor& qkv, at::Tensor& kcache, at:
                                   const c10::optional<at::Tensor>& cos,
                                   const c10::optional<at::Tensor>& sin,
                                   const at::Tensor& cache_idx, long rot, bool interleaved,
-                                  double scale);
+                                  double scale,
+                                  const c10::optional<at::Tensor>& alibi_slopes);
 void decode_advance(const at::Tensor& tok, at::Tensor& out_tokens, at::Tensor& cur_tok,
                     at::Tensor& finished, at::Tensor& rng_offset, at::Tensor& step_col,
                     at::Tensor& cache_idx, at::Tensor& seq_lens, at::Tensor& pos_ids,
@@ -102,17 +104,20 @@ void stage_gemm_v3(const at::Tensor& a, const at::Tensor& w, const c10::optional
                    const c10::optional<at::Tensor>& pstats_out);
 at::Tensor flash_prefill(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
                          const c10::optional<at::Tensor>& key_starts, long start_pos,
-                         double scale, long tk);
+                         double scale, long tk,
+                         const c10::optional<at::Tensor>& alibi_slopes);
 std::vector<at::Tensor> flash_prefill_lse(const at::Tensor& q, const at::Tensor& k,
                                           const at::Tensor& v,
                                           const c10::optional<at::Tensor>& key_starts,
                                           long start_pos, double scale, long tk,
-                                          bool want_lse);
+                                          bool want_lse,
+                                          const c10::optional<at::Tensor>& alibi_slopes);
 std::vector<at::Tensor> flash_prefill_bwd(const at::Tensor& q, const at::Tensor& k,
                                           const at::Tensor& v, const at::Tensor& out,
                                           const at::Tensor& dout, const at::Tensor& lse,
                                           const c10::optional<at::Tensor>& key_starts,
-                                          double scale);
+                                          double scale,
+                                          const c10::optional<at::Tensor>& alibi_slopes);
 void lm_sample_v3(const at::Tensor& x, const at::Tensor& wlm,
                   const c10::optional<at::Tensor>& blm, const at::Tensor& pstats, long nparts,
                   const at::Tensor& nw, const c10::optional<at::Tensor>& nb, at::Tensor& packed,
@@ -141,7 +146,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("qkv_prep_bwd", &qkv_prep_bwd);
   mod.def("causal_softmax_fwd", &causal_softmax_fwd);
   mod.def("causal_softmax_bwd", &causal_softmax_bwd);
-  mod.def("attention_decode", &attention_decode);
+  mod.def("attention_decode", &attention_decode, py::arg("q"), py::arg("k_cache"),
+          py::arg("v_cache"), py::arg("seq_lens"), py::arg("scale"), py::arg("seq_starts"),
+          py::arg("alibi_slopes") = py::none());
   mod.def("fused_adamw", &fused_adamw);
   mod.def("lm_logprobs", &lm_logprobs);
   mod.def("lm_logprobs_v2", &lm_logprobs_v2);
@@ -150,7 +157,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("lm_logprobs_v2_with_lse", &lm_logprobs_v2_with_lse);
   mod.def("ce_dlogits", &ce_dlogits);
   mod.def("decode_advance", &decode_advance);
-  mod.def("fused_decode_attention", &fused_decode_attention);
+  mod.def("fused_decode_attention", &fused_decode_attention, py::arg("qkv"),
+          py::arg("k_cache"), py::arg("v_cache"), py::arg("seq_lens"), py::arg("seq_starts"),
+          py::arg("cos"), py::arg("sin"), py::arg("cache_idx"), py::arg("rot"),
+          py::arg("interleaved"), py::arg("scale"), py::arg("alibi_slopes") = py::none());
   mod.def("stage_gemm", &stage_gemm);
   mod.def("embed_stats", &embed_stats);
   mod.def("lm_sample", &lm_sample);
@@ -159,7 +169,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("lm_sample_v2", &lm_sample_v2);
   mod.def("stage_gemm_v3", &stage_gemm_v3);
   mod.def("lm_sample_v3", &lm_sample_v3);
-  mod.def("flash_prefill", &flash_prefill);
-  mod.def("flash_prefill_lse", &flash_prefill_lse);
-  mod.def("flash_prefill_bwd", &flash_prefill_bwd);
+  // trailing alibi_slopes defaults to None: positional callers keep working
+  mod.def("flash_prefill", &flash_prefill, py::arg("q"), py::arg("k"), py::arg("v"),
+          py::arg("key_starts"), py::arg("start_pos"), py::arg("scale"), py::arg("tk"),
+          py::arg("alibi_slopes") = py::none());
+  mod.def("flash_prefill_lse", &flash_prefill_lse, py::arg("q"), py::arg("k"), py::arg("v"),
+          py::arg("key_starts"), py::arg("start_pos"), py::arg("scale"), py::arg("tk"),
+          py::arg("want_lse"), py::arg("alibi_slopes") = py::none());
+  mod.def("flash_prefill_bwd", &flash_prefill_bwd, py::arg("q"), py::arg("k"), py::arg("v"),
+          py::arg("out"), py::arg("dout"), py::arg("lse"), py::arg("key_starts"),
+          py::arg("scale"), py::arg("alibi_slopes") = py::none());
 }

@@ -173,6 +173,17 @@ DEV MS wave_ms(MS v) {
   return v;
 }
 
+// ---- ALiBi -------------------------------------------------------------------
+
+// scaled score + slope * (key - key_start) in fp32 (Bloom: the bias depends
+// on the key position only).  The flash forward, both flash backward kernels
+// and the decode kernels all call this one helper: the backward recomputes P
+// from the saved logsumexp, so the biased score must round identically there
+// (explicit fma, int->float conversion before the multiply).
+DEV float alibi_score(float score, float slope, int key, int kstart) {
+  return __builtin_fmaf(slope, (float)(key - kstart), score);
+}
+
 // ---- counter-based RNG (splitmix64) -----------------------------------------
 
 DEV unsigned long long splitmix64(unsigned long long z) {
@@ -193,6 +204,22 @@ inline unsigned long long splitmix64_host(unsigned long long z) {
   z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
   z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
   return z ^ (z >> 31);
+}
+
+// host side: validate an optional ALiBi slope vector (fp32, contiguous, same
+// device as `like`, one slope per QUERY head) and return its pointer, or null
+// when no bias was given.  (every kernel file includes ATen before common.h)
+inline const float* alibi_slopes_ptr(const c10::optional<at::Tensor>& slopes,
+                                     const at::Tensor& like, long num_q_heads,
+                                     const char* op) {
+  if (!slopes.has_value()) return nullptr;
+  TORCH_CHECK(slopes->dtype() == at::kFloat && slopes->is_contiguous(), op,
+              ": alibi_slopes must be contiguous fp32");
+  TORCH_CHECK(slopes->device() == like.device(), op,
+              ": alibi_slopes must live on the same device as the inputs");
+  TORCH_CHECK(slopes->numel() == num_q_heads, op, ": alibi_slopes needs one slope per query head (",
+              num_q_heads, "), got ", slopes->numel());
+  return slopes->data_ptr<float>();
 }
 
 #define HIP_CHECK_LAST()                                           \

@@ -93,11 +93,14 @@ DEV bf16x8_fb load_bfragT(const unsigned short* __restrict__ tds, int col, int d
   return r;
 }
 
-template <int D>
+// ALIBI is a template parameter in both kernels (as in the forward): the
+// no-bias instantiations compile to exactly the code they were without it.
+template <int D, bool ALIBI>
 __global__ __launch_bounds__(BBLOCK, 2) void flash_bwd_dkv_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
     const bf16_t* __restrict__ dout, const float* __restrict__ lse,
     const float* __restrict__ drow, const int* __restrict__ key_starts,
+    const float* __restrict__ alibi_slopes /* [Hq]; read iff ALIBI */,
     bf16_t* __restrict__ dk, bf16_t* __restrict__ dv, int B, int Hq, int Hkv, int T,
     float scale) {
   const int kt = blockIdx.x * BT;
@@ -134,6 +137,7 @@ __global__ __launch_bounds__(BBLOCK, 2) void flash_bwd_dkv_kernel(
   }
 
   for (int hq = hkv * rep; hq < (hkv + 1) * rep; ++hq) {
+    const float slope = ALIBI ? alibi_slopes[hq] : 0.f;  // per QUERY head
     for (int qt = kt; qt < T; qt += BT) {  // causal: q-tiles at/after the diagonal
       __syncthreads();
       stage_tileT<D>(q + ((size_t)b * Hq + hq) * (size_t)T * D, qt, T - qt, qT_lds, scale);
@@ -166,6 +170,8 @@ __global__ __launch_bounds__(BBLOCK, 2) void flash_bwd_dkv_kernel(
         for (int r = 0; r < 4; ++r) {
           const int key = kt + krow0 + (lane >> 4) * 4 + r;
           const bool valid = key < T && key >= kstart && key <= qpos && qpos < T;
+          // same biased score the forward folded into L
+          if constexpr (ALIBI) st[r] = alibi_score(st[r], slope, key, kstart);
           const float p = (valid && L < INFINITY) ? __expf(st[r] - L) : 0.f;
           st[r] = p;
           dpt[r] = p * (dpt[r] - Dr);
@@ -220,11 +226,12 @@ __global__ __launch_bounds__(BBLOCK, 2) void flash_bwd_dkv_kernel(
     }
 }
 
-template <int D>
+template <int D, bool ALIBI>
 __global__ __launch_bounds__(BBLOCK, 2) void flash_bwd_dq_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
     const bf16_t* __restrict__ dout, const float* __restrict__ lse,
     const float* __restrict__ drow, const int* __restrict__ key_starts,
+    const float* __restrict__ alibi_slopes /* [Hq]; read iff ALIBI */,
     bf16_t* __restrict__ dq, int B, int Hq, int Hkv, int T, float scale) {
   const int qt = blockIdx.x * BT;
   const int h = blockIdx.y;
@@ -232,6 +239,7 @@ __global__ __launch_bounds__(BBLOCK, 2) void flash_bwd_dq_kernel(
   if (qt >= T) return;
   const int hkv = h / (Hq / Hkv);
   const int kstart = key_starts ? key_starts[b] : 0;
+  const float slope = ALIBI ? alibi_slopes[h] : 0.f;
 
   const int lane = threadIdx.x % WAVE;
   const int wid = threadIdx.x / WAVE;
@@ -287,6 +295,7 @@ __global__ __launch_bounds__(BBLOCK, 2) void flash_bwd_dq_kernel(
       for (int r = 0; r < 4; ++r) {
         const int qrow = qt + qrow0 + (lane >> 4) * 4 + r;
         const bool valid = key < T && key >= kstart && key <= qrow && qrow < T;
+        if constexpr (ALIBI) s[r] = alibi_score(s[r], slope, key, kstart);
         const float p = (valid && L_r[r] < INFINITY) ? __expf(s[r] - L_r[r]) : 0.f;
         s[r] = p * (dp[r] - D_r[r]);  // dS
       }
@@ -325,7 +334,8 @@ std::vector<at::Tensor> flash_prefill_bwd(const at::Tensor& q, const at::Tensor&
                                           const at::Tensor& v, const at::Tensor& out,
                                           const at::Tensor& dout, const at::Tensor& lse,
                                           const c10::optional<at::Tensor>& key_starts,
-                                          double scale) {
+                                          double scale,
+                                          const c10::optional<at::Tensor>& alibi_slopes) {
   TORCH_CHECK(q.is_cuda() && q.dtype() == at::kBFloat16 && q.dim() == 4 && q.is_contiguous(),
               "flash_prefill_bwd: q must be contiguous bf16 [B,Hq,T,D]");
   TORCH_CHECK(k.is_contiguous() && v.is_contiguous() && lse.is_contiguous());
@@ -333,6 +343,7 @@ std::vector<at::Tensor> flash_prefill_bwd(const at::Tensor& q, const at::Tensor&
   const int Hkv = k.size(1);
   TORCH_CHECK(k.size(2) == T, "flash_prefill_bwd: training path only (Tk == T)");
   TORCH_CHECK(Hq % Hkv == 0);
+  const float* sl = alibi_slopes_ptr(alibi_slopes, q, Hq, "flash_prefill_bwd");
   auto dq = at::empty_like(q);
   auto dk = at::empty_like(k);
   auto dv = at::empty_like(v);
@@ -354,18 +365,22 @@ std::vector<at::Tensor> flash_prefill_bwd(const at::Tensor& q, const at::Tensor&
   auto dvp = reinterpret_cast<bf16_t*>(dv.data_ptr());
   dim3 gk((T + BT - 1) / BT, Hkv, B);
   dim3 gq((T + BT - 1) / BT, Hq, B);
-#define LAUNCH_BWD(DV)                                                                    \
+#define LAUNCH_BWD(DV, AL)                                                                \
   do {                                                                                    \
-    flash_bwd_dkv_kernel<DV><<<gk, BBLOCK, 0, stream>>>(                                  \
-        qp, kp, vp, dop, lse.data_ptr<float>(), drow.data_ptr<float>(), ks, dkp, dvp, B,  \
+    flash_bwd_dkv_kernel<DV, AL><<<gk, BBLOCK, 0, stream>>>(                              \
+        qp, kp, vp, dop, lse.data_ptr<float>(), drow.data_ptr<float>(), ks, sl, dkp, dvp, \
+        B, Hq, Hkv, T, (float)scale);                                                     \
+    flash_bwd_dq_kernel<DV, AL><<<gq, BBLOCK, 0, stream>>>(                               \
+        qp, kp, vp, dop, lse.data_ptr<float>(), drow.data_ptr<float>(), ks, sl, dqp, B,   \
         Hq, Hkv, T, (float)scale);                                                        \
-    flash_bwd_dq_kernel<DV><<<gq, BBLOCK, 0, stream>>>(                                   \
-        qp, kp, vp, dop, lse.data_ptr<float>(), drow.data_ptr<float>(), ks, dqp, B, Hq,   \
-        Hkv, T, (float)scale);                                                            \
   } while (0)
   switch (D) {
-    case 64: LAUNCH_BWD(64); break;
-    case 128: LAUNCH_BWD(128); break;
+    case 64:
+      if (sl != nullptr) LAUNCH_BWD(64, true); else LAUNCH_BWD(64, false);
+      break;
+    case 128:
+      if (sl != nullptr) LAUNCH_BWD(128, true); else LAUNCH_BWD(128, false);
+      break;
     default: TORCH_CHECK(false, "flash_prefill_bwd: head dim must be 64 or 128");
   }
 #undef LAUNCH_BWD

@@ -18,6 +18,9 @@
 //     accumulator.
 // Masks follow the causal_softmax/flash-decode conventions: query at global
 // position start_pos + qi sees keys j with key_start[b] <= j <= start_pos+qi.
+// ALiBi (Bloom): optional per-query-head slopes add slope[hq] * (j - key_start[b])
+// to the scaled score fragments right after the QK^T MFMA, in fp32, so the
+// row max / logsumexp include the bias (common.h alibi_score).
 // GQA maps hq -> hkv = hq / (Hq/Hkv).  Backward stays on the materializing
 // path (training attention backward is a later item; the experience forward
 // and prefill are no_grad and dominate PPO's attention time).
@@ -36,11 +39,15 @@ constexpr int TK = 64;  // keys per tile
 typedef __attribute__((ext_vector_type(8))) short bf16x8_fp;
 typedef __attribute__((ext_vector_type(4))) float f32x4_fp;
 
-template <int D>
+// ALIBI is a template parameter (not a runtime null test) so the no-bias
+// instantiation compiles to exactly the code it was before the bias existed.
+template <int D, bool ALIBI>
 __global__ __launch_bounds__(FBLOCK, 2) void flash_prefill_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
-    const int* __restrict__ key_starts, bf16_t* __restrict__ out,
-    float* __restrict__ lse /* [B,Hq,T] logsumexp of the SCALED scores; may be null */,
+    const int* __restrict__ key_starts,
+    const float* __restrict__ alibi_slopes /* [Hq] per query head; read iff ALIBI */,
+    bf16_t* __restrict__ out,
+    float* __restrict__ lse /* [B,Hq,T] logsumexp of the SCALED (+biased) scores; may be null */,
     int B, int Hq, int Hkv, int T, int Tk,
     int Sk /* allocated token stride of k/v (cache prefill) */, int start_pos, float scale) {
   constexpr int DPAD = D + 8;    // LDS row stride (shorts), bank-staggered
@@ -53,6 +60,7 @@ __global__ __launch_bounds__(FBLOCK, 2) void flash_prefill_kernel(
   const int q0 = qt * TQ;
   if (q0 >= T) return;
   const int kstart = key_starts ? key_starts[b] : 0;
+  const float slope = ALIBI ? alibi_slopes[h] : 0.f;
 
   const int lane = threadIdx.x % WAVE;
   const int wid = threadIdx.x / WAVE;
@@ -141,6 +149,10 @@ __global__ __launch_bounds__(FBLOCK, 2) void flash_prefill_kernel(
 #pragma unroll
     for (int kk = 0; kk < TK / 16; ++kk) {
       const int key = kt + kk * 16 + c;
+      if constexpr (ALIBI) {  // Q is pre-scaled in LDS: bias goes on the scaled score
+#pragma unroll
+        for (int r = 0; r < 4; ++r) sfrag[kk][r] = alibi_score(sfrag[kk][r], slope, key, kstart);
+      }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int qrow = q0 + qrow0 + (lane >> 4) * 4 + r;
@@ -237,19 +249,22 @@ __global__ __launch_bounds__(FBLOCK, 2) void flash_prefill_kernel(
 std::vector<at::Tensor> flash_prefill_lse(const at::Tensor& q, const at::Tensor& k,
                                           const at::Tensor& v,
                                           const c10::optional<at::Tensor>& key_starts,
-                                          long start_pos, double scale, long tk, bool want_lse);
+                                          long start_pos, double scale, long tk, bool want_lse,
+                                          const c10::optional<at::Tensor>& alibi_slopes);
 
 at::Tensor flash_prefill(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
                          const c10::optional<at::Tensor>& key_starts, long start_pos,
-                         double scale, long tk) {
-  return flash_prefill_lse(q, k, v, key_starts, start_pos, scale, tk, false)[0];
+                         double scale, long tk,
+                         const c10::optional<at::Tensor>& alibi_slopes) {
+  return flash_prefill_lse(q, k, v, key_starts, start_pos, scale, tk, false, alibi_slopes)[0];
 }
 
 std::vector<at::Tensor> flash_prefill_lse(const at::Tensor& q, const at::Tensor& k,
                                           const at::Tensor& v,
                                           const c10::optional<at::Tensor>& key_starts,
                                           long start_pos, double scale, long tk,
-                                          bool want_lse) {
+                                          bool want_lse,
+                                          const c10::optional<at::Tensor>& alibi_slopes) {
   TORCH_CHECK(q.is_cuda() && q.dtype() == at::kBFloat16 && q.dim() == 4 && q.is_contiguous());
   TORCH_CHECK(k.is_contiguous() && v.is_contiguous());
   const int B = q.size(0), Hq = q.size(1), T = q.size(2), D = q.size(3);
@@ -257,6 +272,7 @@ std::vector<at::Tensor> flash_prefill_lse(const at::Tensor& q, const at::Tensor&
   const int Tk = tk > 0 ? (int)tk : Sk;  // valid keys (<= allocated stride)
   TORCH_CHECK(Tk <= Sk);
   TORCH_CHECK(k.size(3) == D && Hq % Hkv == 0);
+  const float* sl = alibi_slopes_ptr(alibi_slopes, q, Hq, "flash_prefill");
   auto out = at::empty_like(q);
   auto lse = want_lse ? at::empty({B, Hq, T}, q.options().dtype(at::kFloat)) : at::Tensor();
   if (q.numel() == 0) return {out, lse};
@@ -274,18 +290,20 @@ std::vector<at::Tensor> flash_prefill_lse(const at::Tensor& q, const at::Tensor&
   auto vp = reinterpret_cast<const bf16_t*>(v.data_ptr());
   auto op = reinterpret_cast<bf16_t*>(out.data_ptr());
   float* lp = want_lse ? lse.data_ptr<float>() : nullptr;
+#define LAUNCH_FWD(DV, AL)                                                              \
+  flash_prefill_kernel<DV, AL><<<grid, FBLOCK, 0, stream>>>(                            \
+      qp, kp, vp, ks, sl, op, lp, B, Hq, Hkv, T, Tk, Sk, (int)start_pos, (float)scale)
   switch (D) {
     case 64:
-      flash_prefill_kernel<64><<<grid, FBLOCK, 0, stream>>>(
-          qp, kp, vp, ks, op, lp, B, Hq, Hkv, T, Tk, Sk, (int)start_pos, (float)scale);
+      if (sl != nullptr) LAUNCH_FWD(64, true); else LAUNCH_FWD(64, false);
       break;
     case 128:
-      flash_prefill_kernel<128><<<grid, FBLOCK, 0, stream>>>(
-          qp, kp, vp, ks, op, lp, B, Hq, Hkv, T, Tk, Sk, (int)start_pos, (float)scale);
+      if (sl != nullptr) LAUNCH_FWD(128, true); else LAUNCH_FWD(128, false);
       break;
     default:
       TORCH_CHECK(false, "flash_prefill: head dim must be 64 or 128, got ", D);
   }
+#undef LAUNCH_FWD
   HIP_CHECK_LAST();
   return {out, lse};
 }

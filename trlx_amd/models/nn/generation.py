@@ -106,6 +106,7 @@ class FusedStageRefs:
             not cfg.parallel_residual
             and cfg.num_heads == cfg.num_kv_heads
             and cfg.head_dim in (64, 128, 256)
+            # ALiBi stays refused here: the stage-kernel step passes no slopes
             and cfg.position_encoding in ("learned", "rope")
             and not cfg.extra.get("pre_embed_norm")
             and not cfg.swiglu
@@ -443,11 +444,11 @@ def generate(
     try:
         shaping_graphable = shaping_fn is None or gen.graph_safe_shaping
         has_virtual = getattr(model, "num_virtual_tokens", 0) > 0
-        alibi = getattr(model.config, "position_encoding", None) == "alibi"
         # the graph engine needs the fused decode kernels (device-side cache
-        # index); unsupported head dims use the eager loop's host-side state
+        # index); unsupported head dims use the eager loop's host-side state.
+        # ALiBi models qualify: the decode kernels take the head slopes.
         head_ok = getattr(model.config, "head_dim", 64) in (32, 64, 128, 256)
-        if (device.type == "cuda" and shaping_graphable and gen.use_graph and not alibi
+        if (device.type == "cuda" and shaping_graphable and gen.use_graph
                 and head_ok and not has_virtual
                 and _graphs_enabled() and gen.max_new_tokens > 1 and gen.min_new_tokens == 0):
             engine = getattr(model, "_decode_engine", None)

@@ -88,11 +88,28 @@ class AttentionContext:
     # PER-ROW cache write positions [B] (continuous-batching decode: slots
     # sit at different depths); mutually exclusive with cache_idx
     cache_rows: Optional[torch.Tensor] = None
-    # ALiBi additive bias [B, H_local, 1, T_keys] (Bloom)
+    # ALiBi (Bloom): per-head slopes [H_local] fp32.  The flash and decode
+    # kernels take these directly and add slope * (key - key_start) in-tile
+    alibi_slopes: Optional[torch.Tensor] = None
+    # dense ALiBi bias [B, H_local, 1, T_keys]: built lazily by dense_alibi()
+    # and ONLY for the materializing attention path (never in a graph step)
     alibi: Optional[torch.Tensor] = None
     # PREFIX_TUNING: per-layer K/V params + the cache positions they occupy
     prefix_kv: Optional[object] = None
     virtual_slots: Optional[torch.Tensor] = None  # [B, n] long
+
+    def dense_alibi(self, batch: int, num_keys: int) -> torch.Tensor:
+        """ALiBi bias per KEY position (Bloom semantics: mask-aware positions,
+        pads at bias 0) as a dense [B, H_local, 1, num_keys] fp32 tensor that
+        broadcasts over queries; cached across the layers of one forward."""
+        if self.alibi is None or self.alibi.shape[-1] != num_keys:
+            slopes = self.alibi_slopes
+            j = torch.arange(num_keys, device=slopes.device).unsqueeze(0)
+            ks = (self.key_starts.unsqueeze(1) if self.key_starts is not None
+                  else torch.zeros(batch, 1, device=slopes.device))
+            key_pos = (j - ks).clamp(min=0).float()  # [B, Tk]
+            self.alibi = slopes.view(1, -1, 1, 1) * key_pos[:, None, None, :]
+        return self.alibi
 
 
 class KVCache:
@@ -165,7 +182,7 @@ class Attention(nn.Module):
         # fused single-token decode path: decode_prep (split+RoPE+cache
         # append) + flash-decode attention, fully device-side (hipGraph-safe)
         if (T == 1 and kv_cache is not None and ctx.cache_idx is not None
-                and ctx.seq_lens is not None and x.is_cuda and ctx.alibi is None
+                and ctx.seq_lens is not None and x.is_cuda
                 and self.head_dim in (32, 64, 128, 256)):
             # (unsupported head dims fall through to the eager T=1 math below)
             cos_sin = rope_tables if self.cfg.position_encoding == "rope" else (None, None)
@@ -176,6 +193,7 @@ class Attention(nn.Module):
                     qkv, kv_cache.k[self.layer_idx], kv_cache.v[self.layer_idx],
                     ctx.seq_lens, ctx.key_starts, cos_sin[0], cos_sin[1], ctx.cache_idx,
                     self.rot, self.cfg.rope_interleaved, self.scale,
+                    alibi_slopes=ctx.alibi_slopes,
                 )
             else:
                 q = ops.decode_prep(
@@ -185,7 +203,8 @@ class Attention(nn.Module):
                 )
                 out = ops.attention_decode(q, kv_cache.k[self.layer_idx],
                                            kv_cache.v[self.layer_idx],
-                                           ctx.seq_lens, self.scale, seq_starts=ctx.key_starts)
+                                           ctx.seq_lens, self.scale, seq_starts=ctx.key_starts,
+                                           alibi_slopes=ctx.alibi_slopes)
             return dense(self.o_proj, out.transpose(1, 2).reshape(B, T, -1))
 
         if x.is_cuda and x.dtype == torch.bfloat16 and ops.extension_available():
@@ -223,7 +242,7 @@ class Attention(nn.Module):
 
         flash_ok = (
             T > 1 and x.is_cuda and q.dtype == torch.bfloat16
-            and self.head_dim in (64, 128) and ctx.alibi is None
+            and self.head_dim in (64, 128)
             and not torch.is_grad_enabled()
             and (self.attn_pdrop == 0 or not self.training)
             and ops.extension_available()
@@ -244,7 +263,8 @@ class Attention(nn.Module):
                 # decode path on GPU — caught by the ctx-level decode test)
                 out = ops.attention_decode(q, k_full, v_full, ctx.seq_lens,
                                            1.0 if pre_scaled else self.scale,
-                                           seq_starts=ctx.key_starts)
+                                           seq_starts=ctx.key_starts,
+                                           alibi_slopes=ctx.alibi_slopes)
                 out = out.transpose(1, 2).reshape(B, T, -1)
                 return dense(self.o_proj, out)
             if flash_ok:
@@ -252,7 +272,7 @@ class Attention(nn.Module):
                 # tensors in place (allocated stride Sk, valid start_pos+T)
                 out = ops.flash_prefill(q, k_full, v_full, ctx.key_starts, ctx.start_pos,
                                         1.0 if pre_scaled else self.scale,
-                                        tk=ctx.start_pos + T)
+                                        tk=ctx.start_pos + T, alibi_slopes=ctx.alibi_slopes)
                 out = out.transpose(1, 2).reshape(B, T, -1)
                 return dense(self.o_proj, out)
             k = k_full[:, :, : ctx.start_pos + T]
@@ -263,13 +283,14 @@ class Attention(nn.Module):
             # (the memory wall at seq 1024-2048)
             out = ops.flash_prefill(q.contiguous(), k.contiguous(), v.contiguous(),
                                     ctx.key_starts, ctx.start_pos,
-                                    1.0 if pre_scaled else self.scale)
+                                    1.0 if pre_scaled else self.scale,
+                                    alibi_slopes=ctx.alibi_slopes)
             out = out.transpose(1, 2).reshape(B, T, -1)
             return dense(self.o_proj, out)
 
         flash_train_ok = (
             T > 1 and x.is_cuda and q.dtype == torch.bfloat16
-            and self.head_dim in (64, 128) and ctx.alibi is None
+            and self.head_dim in (64, 128)
             and torch.is_grad_enabled() and kv_cache is None and ctx.start_pos == 0
             and (self.attn_pdrop == 0 or not self.training)
             and ops.extension_available()
@@ -282,7 +303,8 @@ class Attention(nn.Module):
             # (csrc/flash_backward.hip); [B, H, T, T] never materializes in
             # either direction
             out = ops.flash_attention(q, k, v, ctx.key_starts,
-                                      1.0 if pre_scaled else self.scale)
+                                      1.0 if pre_scaled else self.scale,
+                                      alibi_slopes=ctx.alibi_slopes)
             out = out.transpose(1, 2).reshape(B, T, -1)
             return dense(self.o_proj, out)
 
@@ -293,8 +315,10 @@ class Attention(nn.Module):
             v = v.repeat_interleave(rep, dim=1)
         qs = q if pre_scaled else q * self.scale
         scores = torch.matmul(qs, k.transpose(-1, -2))
-        if ctx.alibi is not None:
-            scores = scores + ctx.alibi[:, :, :, : scores.shape[-1]].to(scores.dtype)
+        if ctx.alibi_slopes is not None:
+            # the one consumer of the dense [B, H, 1, Tk] bias (built here, on
+            # demand: the kernels above take the slopes themselves)
+            scores = scores + ctx.dense_alibi(B, scores.shape[-1]).to(scores.dtype)
         probs = ops.causal_softmax(scores.contiguous(), ctx.start_pos, ctx.key_starts)
         if self.attn_pdrop > 0 and self.training:
             probs = F.dropout(probs, self.attn_pdrop)
@@ -488,8 +512,30 @@ class CausalTransformer(nn.Module):
             self.register_buffer("rope_sin", sin, persistent=False)
         else:
             self.rope_cos = self.rope_sin = None
+        # ALiBi head slopes (this TP rank's heads), built once: a per-forward
+        # host->device copy could not be captured into the decode graph
+        self.register_buffer("alibi_slopes", self._local_alibi_slopes(), persistent=False)
         self.sequence_parallel = False
         self.apply(self._init_weights)
+
+    def _local_alibi_slopes(self) -> Optional[torch.Tensor]:
+        if self.config.position_encoding != "alibi":
+            return None
+        slopes = alibi_slopes(self.config.num_heads)
+        tp = topo.tp_size()
+        if tp > 1:
+            hl = self.config.num_heads // tp
+            slopes = slopes[topo.tp_rank() * hl : (topo.tp_rank() + 1) * hl].contiguous()
+        return slopes
+
+    def _apply(self, fn, *args, **kwargs):
+        # .to(bf16)/.half() cast every floating buffer; the kernels need the
+        # slopes in fp32 at full precision, so rebuild them after a dtype cast
+        super()._apply(fn, *args, **kwargs)
+        buf = self._buffers.get("alibi_slopes")
+        if buf is not None and buf.dtype != torch.float32:
+            self._buffers["alibi_slopes"] = self._local_alibi_slopes().to(buf.device)
+        return self
 
     def set_sequence_parallel(self, enabled: bool):
         """Toggle Megatron-style sequence parallelism (activations sharded
@@ -558,7 +604,8 @@ class CausalTransformer(nn.Module):
                 .unsqueeze(0).expand(B, T).contiguous()
             )
         return AttentionContext(position_ids=position_ids, key_starts=key_starts,
-                                start_pos=start_pos, seq_lens=seq_lens)
+                                start_pos=start_pos, seq_lens=seq_lens,
+                                alibi_slopes=self.alibi_slopes)
 
     def run_layers(self, h, ctx, kv_cache=None, from_layer: int = 0, to_layer: Optional[int] = None):
         to_layer = len(self.layers) if to_layer is None else to_layer
@@ -615,22 +662,6 @@ class CausalTransformer(nn.Module):
             h = h + self.embed_positions(ctx.position_ids.long() + off)
         if self.embd_pdrop > 0 and self.training:
             h = F.dropout(h, self.embd_pdrop)
-
-        if self.config.position_encoding == "alibi":
-            # ALiBi bias per KEY position (Bloom semantics: mask-aware
-            # positions, pads at bias 0); broadcasts over queries and covers
-            # the cached keys during decode
-            tp = topo.tp_size()
-            slopes = alibi_slopes(self.config.num_heads).to(h.device)
-            if tp > 1:
-                hl = self.config.num_heads // tp
-                slopes = slopes[topo.tp_rank() * hl : (topo.tp_rank() + 1) * hl]
-            B, T = input_ids.shape[:2]
-            Tk = start_pos + T
-            j = torch.arange(Tk, device=h.device).unsqueeze(0)
-            ks = ctx.key_starts.unsqueeze(1) if ctx.key_starts is not None else torch.zeros(B, 1, device=h.device)
-            key_pos = (j - ks).clamp(min=0).float()  # [B, Tk]
-            ctx.alibi = slopes.view(1, -1, 1, 1) * key_pos[:, None, None, :]
 
         # sequence parallelism: shard activations along T for the
         # norm/residual segments (SP stays off for KV-cached generation)

@@ -562,17 +562,20 @@ def fused_decode_attention(
     rot: int,
     interleaved: bool,
     scale: float,
+    alibi_slopes: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
     """MHA decode step in ONE kernel: split fused qkv, RoPE q/k, append k/v
     to the cache at *cache_idx, flash-decode attention — out [B,H,1,D].
-    GPU-only (the eager path covers CPU); requires Hq == Hkv."""
+    GPU-only (the eager path covers CPU); requires Hq == Hkv.
+    ``alibi_slopes`` [H] fp32 adds ``slope[h] * (key - key_starts[b])`` to the
+    scaled scores (Bloom; not combinable with RoPE tables)."""
     ext = _require_ext("fused_decode_attention")
     ks = key_starts.to(torch.int32).contiguous() if key_starts is not None else None
     if cos is not None and cos.dtype != torch.float32:
         cos, sin = cos.float(), sin.float()  # kernels require fp32 trig tables
     return ext.fused_decode_attention(qkv.contiguous(), k_cache, v_cache,
                                       seq_lens.to(torch.int32).contiguous(), ks, cos, sin,
-                                      cache_idx, rot, interleaved, scale)
+                                      cache_idx, rot, interleaved, scale, alibi_slopes)
 
 
 class _QKVPrep(torch.autograd.Function):
@@ -713,13 +716,16 @@ def attention_decode(
     seq_lens: torch.Tensor,
     scale: float,
     seq_starts: Optional[torch.Tensor] = None,
+    alibi_slopes: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
     """Fused decode attention: q [B, Hq, 1, D] vs cache [B, Hkv, S, D]
     with per-row valid key range [seq_starts[b], seq_lens[b]) -> [B, Hq, 1, D]
     (``seq_starts`` handles left-padded prompts).
 
     Memory-bound flash-decode kernel; online softmax, no
-    [B, H, S] score materialization.
+    [B, H, S] score materialization.  ``alibi_slopes`` [Hq] fp32 (one slope
+    per QUERY head) adds ``slope[h] * (key - seq_starts[b])`` to the scaled
+    scores (Bloom).
     """
     if q.is_cuda:
         ext = _require_ext("attention_decode")
@@ -727,7 +733,7 @@ def attention_decode(
             ss = None if seq_starts is None else seq_starts.to(torch.int32).contiguous()
             return ext.attention_decode(
                 q.contiguous(), k_cache.contiguous(), v_cache.contiguous(),
-                seq_lens.to(torch.int32).contiguous(), scale, ss,
+                seq_lens.to(torch.int32).contiguous(), scale, ss, alibi_slopes,
             )
     # reference: masked SDPA
     B, Hq, _, D = q.shape
@@ -745,6 +751,9 @@ def attention_decode(
     mask = pos >= seq_lens.view(B, 1, 1, 1)
     if seq_starts is not None:
         mask = mask | (pos < seq_starts.view(B, 1, 1, 1))
+    if alibi_slopes is not None:
+        key_pos = pos if seq_starts is None else (pos - seq_starts.view(B, 1, 1, 1)).clamp(min=0)
+        scores = scores + alibi_slopes.float().view(1, Hq, 1, 1) * key_pos.float()
     scores = scores.masked_fill(mask, float("-inf"))
     probs = torch.softmax(scores, dim=-1)
     return torch.matmul(probs, vf).to(q.dtype)
@@ -787,18 +796,21 @@ def causal_softmax(
 
 
 def flash_prefill(q, k, v, key_starts=None, start_pos: int = 0, scale: float = 1.0,
-                  tk=None):
+                  tk=None, alibi_slopes=None):
     """Forward-only flash attention for prefill / the no_grad experience pass
     (csrc/flash_prefill.hip): q [B,Hq,T,D] (bf16), k/v [B,Hkv,Sk,D] with the
     first ``tk`` tokens valid (cache prefill passes the whole cache), causal +
-    left-pad masking via ``key_starts``.  Returns [B,Hq,T,D] bf16; the
-    [B,H,T,T] scores never materialize."""
+    left-pad masking via ``key_starts``.  ``alibi_slopes`` [Hq] fp32 adds
+    ``slope[h] * (key - key_starts[b])`` to the scaled scores inside the tile
+    loop (Bloom).  Returns [B,Hq,T,D] bf16; the [B,H,T,T] scores never
+    materialize."""
     ext = _require_ext("flash_prefill")
     if ext is None or not q.is_cuda:
-        return reference.flash_prefill(q, k, v, key_starts, start_pos, scale, tk)
+        return reference.flash_prefill(q, k, v, key_starts, start_pos, scale, tk,
+                                       alibi_slopes=alibi_slopes)
     ks = key_starts.to(torch.int32).contiguous() if key_starts is not None else None
     return ext.flash_prefill(q.contiguous(), k, v, ks, int(start_pos), float(scale),
-                             int(tk) if tk is not None else 0)
+                             int(tk) if tk is not None else 0, alibi_slopes)
 
 
 class _FlashAttention(torch.autograd.Function):
@@ -808,9 +820,11 @@ class _FlashAttention(torch.autograd.Function):
     materialize in either direction."""
 
     @staticmethod
-    def forward(ctx, q, k, v, key_starts, scale, ext):
-        out, lse = ext.flash_prefill_lse(q, k, v, key_starts, 0, float(scale), 0, True)
+    def forward(ctx, q, k, v, key_starts, scale, ext, alibi_slopes=None):
+        out, lse = ext.flash_prefill_lse(q, k, v, key_starts, 0, float(scale), 0, True,
+                                         alibi_slopes)
         ctx.save_for_backward(q, k, v, out, lse)
+        ctx.alibi_slopes = alibi_slopes  # constant (not trainable): no grad
         ctx.key_starts = key_starts
         ctx.scale = scale
         ctx.ext = ext
@@ -820,18 +834,19 @@ class _FlashAttention(torch.autograd.Function):
     def backward(ctx, dout):
         q, k, v, out, lse = ctx.saved_tensors
         dq, dk, dv = ctx.ext.flash_prefill_bwd(q, k, v, out, dout, lse, ctx.key_starts,
-                                               float(ctx.scale))
-        return dq, dk, dv, None, None, None
+                                               float(ctx.scale), ctx.alibi_slopes)
+        return dq, dk, dv, None, None, None, None
 
 
-def flash_attention(q, k, v, key_starts=None, scale: float = 1.0):
+def flash_attention(q, k, v, key_starts=None, scale: float = 1.0, alibi_slopes=None):
     """Differentiable flash attention for the TRAINING forward (full causal
     self-attention, no cache): q [B,Hq,T,D] bf16, k/v [B,Hkv,T,D].  On CPU or
     without the extension, falls back to the fp32 reference (autograd handles
     the backward there)."""
     ext = _require_ext("flash_attention")
     if ext is None or not q.is_cuda:
-        return reference.flash_prefill(q, k, v, key_starts, 0, scale).to(q.dtype)
+        return reference.flash_prefill(q, k, v, key_starts, 0, scale,
+                                       alibi_slopes=alibi_slopes).to(q.dtype)
     ks = key_starts.to(torch.int32).contiguous() if key_starts is not None else None
     return _FlashAttention.apply(q.contiguous(), k.contiguous(), v.contiguous(), ks,
-                                 float(scale), ext)
+                                 float(scale), ext, alibi_slopes)

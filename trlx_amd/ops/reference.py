@@ -225,9 +225,12 @@ def fused_adamw(
         p.copy_(mp.to(p.dtype))
 
 
-def flash_prefill(q, k, v, key_starts=None, start_pos: int = 0, scale: float = 1.0, tk=None):
+def flash_prefill(q, k, v, key_starts=None, start_pos: int = 0, scale: float = 1.0, tk=None,
+                  alibi_slopes=None):
     """fp32 reference for the flash prefill kernel (masking semantics match
-    causal_softmax: key j visible to query i iff key_start <= j <= start_pos+i)."""
+    causal_softmax: key j visible to query i iff key_start <= j <= start_pos+i).
+    ``alibi_slopes`` [Hq] adds slope[h] * max(j - key_start, 0) to the scaled
+    scores (ALiBi; the bias depends on the key position only)."""
     B, Hq, T, D = q.shape
     Hkv, Sk = k.shape[1], k.shape[2]
     tkv = int(tk) if tk else Sk
@@ -243,6 +246,10 @@ def flash_prefill(q, k, v, key_starts=None, start_pos: int = 0, scale: float = 1
     mask = j <= (start_pos + i)
     if key_starts is not None:
         mask = mask & (j >= key_starts.view(B, 1, 1, 1).to(q.device))
+    if alibi_slopes is not None:
+        key_pos = j if key_starts is None else j - key_starts.view(B, 1, 1, 1).to(q.device)
+        scores = scores + (alibi_slopes.float().to(q.device).view(1, Hq, 1, 1)
+                           * key_pos.clamp(min=0).float())
     scores = scores.masked_fill(~mask, float("-inf"))
     probs = torch.softmax(scores, dim=-1)
     probs = torch.nan_to_num(probs, nan=0.0)
