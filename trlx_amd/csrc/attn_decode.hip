@@ -16,6 +16,16 @@ namespace {
 constexpr int BLOCK = 256;
 constexpr int NWAVES = BLOCK / WAVE;
 
+// Lane mapping: G = D/8 lanes hold one key's D elements (16 B each) and sit in
+// a group of GL lanes, GL = G rounded up to a power of two, so a wave covers
+// WAVE/GL keys per iteration and the dot product reduces with xor-shuffles
+// over GL/2..1.  For D in {32, 64, 128, 256} GL == G (every lane active, the
+// `if constexpr (GL != G)` branches vanish).  D=96 (NeoX-20B) has G = 12 in
+// 16-lane groups: lanes 12..15 of each group hold q = 0, skip their K/V loads
+// and their o_buf slice, and contribute 0 to the reduction — 4 keys per wave
+// at 48 of 64 lanes loading.
+constexpr int decode_gl(int G) { return G <= 4 ? 4 : G <= 8 ? 8 : G <= 16 ? 16 : 32; }
+
 // ALIBI is a template parameter in both kernels (not a runtime null test):
 // the no-bias instantiations compile to exactly the code they were without it.
 template <int D, bool ALIBI>
@@ -25,7 +35,8 @@ __global__ void attn_decode_kernel(const bf16_t* __restrict__ q, const bf16_t* _
                                    const float* __restrict__ alibi_slopes /* [Hq], iff ALIBI */,
                                    bf16_t* __restrict__ out, int Hq, int Hkv, int S, float scale) {
   constexpr int G = D / 8;          // lanes cooperating on one key
-  constexpr int KPW = WAVE / G;     // keys per wave per iteration
+  constexpr int GL = decode_gl(G);  // lane stride between keys (== G unless D=96)
+  constexpr int KPW = WAVE / GL;    // keys per wave per iteration
   constexpr int NPART = NWAVES * KPW;  // independent (m, s, o) partials
 
   const int b = blockIdx.x / Hq;
@@ -37,8 +48,9 @@ __global__ void attn_decode_kernel(const bf16_t* __restrict__ q, const bf16_t* _
 
   const int lane = threadIdx.x % WAVE;
   const int wid = threadIdx.x / WAVE;
-  const int kgrp = lane / G;        // which key within the wave's group
-  const int d0 = (lane % G) * 8;    // this lane's slice of D
+  const int kgrp = lane / GL;       // which key within the wave's group
+  const int d0 = (lane % GL) * 8;   // this lane's slice of D
+  const bool active = GL == G || d0 < D;  // false on the padding lanes at D=96
 
   const bf16_t* qp = q + ((size_t)b * Hq + hq) * D;
   const bf16_t* kbase = kc + ((size_t)b * Hkv + hkv) * S * D;
@@ -46,7 +58,13 @@ __global__ void attn_decode_kernel(const bf16_t* __restrict__ q, const bf16_t* _
 
   // q fragment for this lane's d-slice
   float qf[8];
-  load8<bf16_t>(qp + d0, qf);
+  if constexpr (GL != G) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) qf[i] = 0.f;
+    if (active) load8<bf16_t>(qp + d0, qf);
+  } else {
+    load8<bf16_t>(qp + d0, qf);
+  }
 #pragma unroll
   for (int i = 0; i < 8; ++i) qf[i] *= scale;
 
@@ -59,14 +77,23 @@ __global__ void attn_decode_kernel(const bf16_t* __restrict__ q, const bf16_t* _
     const int key = sbase + kgrp;
     if (key < len) {
       float kf[8], vf[8];
-      load8<bf16_t>(kbase + (size_t)key * D + d0, kf);
-      load8<bf16_t>(vbase + (size_t)key * D + d0, vf);
+      if constexpr (GL != G) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) kf[i] = vf[i] = 0.f;
+        if (active) {
+          load8<bf16_t>(kbase + (size_t)key * D + d0, kf);
+          load8<bf16_t>(vbase + (size_t)key * D + d0, vf);
+        }
+      } else {
+        load8<bf16_t>(kbase + (size_t)key * D + d0, kf);
+        load8<bf16_t>(vbase + (size_t)key * D + d0, vf);
+      }
       float partial = 0.f;
 #pragma unroll
       for (int i = 0; i < 8; ++i) partial += qf[i] * kf[i];
-      // reduce across the G lanes of this key group (contiguous lanes)
+      // reduce across the GL lanes of this key group (contiguous lanes)
 #pragma unroll
-      for (int off = G / 2; off > 0; off >>= 1) partial += __shfl_xor(partial, off);
+      for (int off = GL / 2; off > 0; off >>= 1) partial += __shfl_xor(partial, off);
       const float score = ALIBI ? alibi_score(partial, slope, key, kstart) : partial;
       // branchless online update (first valid key: m=-inf -> corr=0)
       const float mnew = fmaxf(m, score);
@@ -83,12 +110,14 @@ __global__ void attn_decode_kernel(const bf16_t* __restrict__ q, const bf16_t* _
   __shared__ float ms_buf[NPART][2];
   __shared__ float o_buf[NPART][D];
   const int part = wid * KPW + kgrp;
-  if (lane % G == 0) {
+  if (lane % GL == 0) {
     ms_buf[part][0] = m;
     ms_buf[part][1] = s;
   }
+  if (active) {  // padding lanes own no slice of o_buf[part][D]
 #pragma unroll
-  for (int i = 0; i < 8; ++i) o_buf[part][d0 + i] = o[i];
+    for (int i = 0; i < 8; ++i) o_buf[part][d0 + i] = o[i];
+  }
   __syncthreads();
 
   // final combine: thread t handles output dim t (D <= BLOCK)
@@ -130,7 +159,8 @@ __global__ void fused_decode_attn_kernel(const bf16_t* __restrict__ qkv, bf16_t*
                                          bf16_t* __restrict__ out, int H, int S, int rot,
                                          float scale) {
   constexpr int G = D / 8;
-  constexpr int KPW = WAVE / G;
+  constexpr int GL = decode_gl(G);
+  constexpr int KPW = WAVE / GL;
   constexpr int NPART = NWAVES * KPW;
 
   const int b = blockIdx.x / H;
@@ -187,13 +217,14 @@ __global__ void fused_decode_attn_kernel(const bf16_t* __restrict__ qkv, bf16_t*
   __syncthreads();
 
   // ---- stage 2: flash-decode over the cache (incl. the new key) --------
-  const int kgrp = lane / G;
-  const int d0 = (lane % G) * 8;
+  const int kgrp = lane / GL;
+  const int d0 = (lane % GL) * 8;
+  const bool active = GL == G || d0 < D;
   const bf16_t* kbase = kc + ((size_t)b * H + h) * S * D;
   const bf16_t* vbase = vc + ((size_t)b * H + h) * S * D;
   float qf[8];
 #pragma unroll
-  for (int i = 0; i < 8; ++i) qf[i] = q_lds[d0 + i];
+  for (int i = 0; i < 8; ++i) qf[i] = active ? q_lds[d0 + i] : 0.f;
 
   float m = -INFINITY, s = 0.f;
   float o[8];
@@ -203,13 +234,22 @@ __global__ void fused_decode_attn_kernel(const bf16_t* __restrict__ qkv, bf16_t*
     const int key = sbase + kgrp;
     if (key < len) {
       float kf[8], vf[8];
-      load8<bf16_t>(kbase + (size_t)key * D + d0, kf);
-      load8<bf16_t>(vbase + (size_t)key * D + d0, vf);
+      if constexpr (GL != G) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) kf[i] = vf[i] = 0.f;
+        if (active) {
+          load8<bf16_t>(kbase + (size_t)key * D + d0, kf);
+          load8<bf16_t>(vbase + (size_t)key * D + d0, vf);
+        }
+      } else {
+        load8<bf16_t>(kbase + (size_t)key * D + d0, kf);
+        load8<bf16_t>(vbase + (size_t)key * D + d0, vf);
+      }
       float partial = 0.f;
 #pragma unroll
       for (int i = 0; i < 8; ++i) partial += qf[i] * kf[i];
 #pragma unroll
-      for (int off = G / 2; off > 0; off >>= 1) partial += __shfl_xor(partial, off);
+      for (int off = GL / 2; off > 0; off >>= 1) partial += __shfl_xor(partial, off);
       const float score = ALIBI ? alibi_score(partial, slope, key, kstart) : partial;
       const float mnew = fmaxf(m, score);
       const float corr = (m > -INFINITY) ? __expf(m - mnew) : 0.f;
@@ -224,12 +264,14 @@ __global__ void fused_decode_attn_kernel(const bf16_t* __restrict__ qkv, bf16_t*
   __shared__ float ms_buf[NPART][2];
   __shared__ float o_buf[NPART][D];
   const int part = wid * KPW + kgrp;
-  if (lane % G == 0) {
+  if (lane % GL == 0) {
     ms_buf[part][0] = m;
     ms_buf[part][1] = s;
   }
+  if (active) {  // padding lanes own no slice of o_buf[part][D]
 #pragma unroll
-  for (int i = 0; i < 8; ++i) o_buf[part][d0 + i] = o[i];
+    for (int i = 0; i < 8; ++i) o_buf[part][d0 + i] = o[i];
+  }
   __syncthreads();
   if (threadIdx.x < D) {
     float mstar = -INFINITY;
@@ -307,9 +349,10 @@ at::Tensor fused_decode_attention(const at::Tensor& qkv, at::Tensor& kcache, at:
   switch (D) {
     case 32: LAUNCH_FUSED(32); break;
     case 64: LAUNCH_FUSED(64); break;
+    case 96: LAUNCH_FUSED(96); break;
     case 128: LAUNCH_FUSED(128); break;
     case 256: LAUNCH_FUSED(256); break;
-    default: TORCH_CHECK(false, "fused_decode_attention: head dim must be 32/64/128/256");
+    default: TORCH_CHECK(false, "fused_decode_attention: head dim must be 32/64/96/128/256");
   }
 #undef LAUNCH_FUSED
   HIP_CHECK_LAST();
@@ -356,10 +399,11 @@ at::Tensor attention_decode(const at::Tensor& q, const at::Tensor& kc, const at:
   switch (D) {
     case 32: LAUNCH_DECODE(32); break;
     case 64: LAUNCH_DECODE(64); break;
+    case 96: LAUNCH_DECODE(96); break;
     case 128: LAUNCH_DECODE(128); break;
     case 256: LAUNCH_DECODE(256); break;
     default:
-      TORCH_CHECK(false, "attention_decode: head dim must be 32/64/128/256, got ", D);
+      TORCH_CHECK(false, "attention_decode: head dim must be 32/64/96/128/256, got ", D);
   }
 #undef LAUNCH_DECODE
   HIP_CHECK_LAST();

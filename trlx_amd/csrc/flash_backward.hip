@@ -27,6 +27,13 @@
 //   * P^T / dS^T / dS relayout (D-fragment -> A-operand) goes through a
 //     wave-private [16, 64+8] LDS buffer, reused sequentially — same trick
 //     as the forward's P relayout (flash_prefill.hip).
+// Head dims: 64, 96, 128, 256.  D=96 is the same plan (D/32 = 3 k-steps).  At
+// D=256 the two transposed staging tiles at 64 rows are 73.7 KB, so the
+// staged tile narrows to 32 rows ([D, 32+8] x 2 + p_lds = 46 KB static);
+// each block still owns 64 keys (dKV) or 64 queries (dQ) in registers and
+// just takes twice as many staging steps.  Both new head dims measured slower
+// than the materializing path in training (profiles/headdim_notes.md), so
+// models take them only when asked (ops.flash_enabled): the O(T)-memory path.
 // Masking (causal + left-pad key_starts) matches the forward; fully-masked
 // query rows carry L = +inf so P == 0 and they contribute nothing.
 #include <ATen/ATen.h>
@@ -37,19 +44,27 @@
 namespace {
 
 constexpr int BBLOCK = 256;
-constexpr int BT = 64;  // tile size (both queries and keys)
-constexpr int KPAD = BT + 8;
+constexpr int BT = 64;  // rows a block owns in registers (keys in dKV, queries in dQ)
+// rows of the contraction-side tile staged per step: 64, narrowed to 32 at
+// D=256 where two [D, 64+8] tiles (73.7 KB) exceed the static-LDS limit
+constexpr int bwd_st(int D) { return D > 128 ? 32 : 64; }
+// dKV keeps k_frag + v_frag (D/4 VGPRs) and dv_acc + dk_acc (D/2 VGPRs)
+// resident: 192 of the 256 registers a wave gets at two waves per SIMD when
+// D=256, and the tile loop's working set on top of that spills.  That one
+// instantiation asks for one wave per SIMD (512 registers, no scratch).
+constexpr int dkv_waves(int D) { return D > 128 ? 1 : 2; }
 
 typedef __attribute__((ext_vector_type(8))) short bf16x8_fb;
 typedef __attribute__((ext_vector_type(4))) float f32x4_fb;
 
-// block-wide: stage a [BT, D] bf16 tile TRANSPOSED into tds [D, KPAD],
+// block-wide: stage a [ST, D] bf16 tile TRANSPOSED into tds [D, ST+8],
 // scaling by mul; rows past `nrows` clamp to the last valid row (their
-// columns are masked out of P later).
-template <int D>
+// columns are masked out of P later).  Callers pass nrows >= 1.
+template <int D, int ST>
 DEV void stage_tileT(const bf16_t* __restrict__ src, long row0, long nrows,
                      unsigned short* __restrict__ tds, float mul) {
-  for (int i = threadIdx.x; i < BT * (D / 8); i += BBLOCK) {
+  constexpr int KPAD = ST + 8;
+  for (int i = threadIdx.x; i < ST * (D / 8); i += BBLOCK) {
     const int row = i / (D / 8);
     const int col = (i % (D / 8)) * 8;
     const bf16_t* p = src + (size_t)(row0 + min((long)row, nrows - 1)) * D + col;
@@ -86,6 +101,7 @@ DEV void load_afrag(const bf16_t* __restrict__ src, long row0, long rowmax, int 
 
 // strided B-operand fragment from a transposed [D, KPAD] tile: output row =
 // tile row `col` (query/key index), k-slice elements d = dch*32 + g8 + j.
+template <int KPAD>
 DEV bf16x8_fb load_bfragT(const unsigned short* __restrict__ tds, int col, int dch, int g8) {
   bf16x8_fb r;
 #pragma unroll
@@ -96,13 +112,15 @@ DEV bf16x8_fb load_bfragT(const unsigned short* __restrict__ tds, int col, int d
 // ALIBI is a template parameter in both kernels (as in the forward): the
 // no-bias instantiations compile to exactly the code they were without it.
 template <int D, bool ALIBI>
-__global__ __launch_bounds__(BBLOCK, 2) void flash_bwd_dkv_kernel(
+__global__ __launch_bounds__(BBLOCK, dkv_waves(D)) void flash_bwd_dkv_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
     const bf16_t* __restrict__ dout, const float* __restrict__ lse,
     const float* __restrict__ drow, const int* __restrict__ key_starts,
     const float* __restrict__ alibi_slopes /* [Hq]; read iff ALIBI */,
     bf16_t* __restrict__ dk, bf16_t* __restrict__ dv, int B, int Hq, int Hkv, int T,
     float scale) {
+  constexpr int ST = bwd_st(D);  // queries staged per step
+  constexpr int KPAD = ST + 8;
   const int kt = blockIdx.x * BT;
   const int hkv = blockIdx.y;
   const int b = blockIdx.z;
@@ -118,8 +136,8 @@ __global__ __launch_bounds__(BBLOCK, 2) void flash_bwd_dkv_kernel(
 
   __shared__ unsigned short qT_lds[D * KPAD];
   __shared__ unsigned short doT_lds[D * KPAD];
-  __shared__ float l_lds[BT];
-  __shared__ float d_lds[BT];
+  __shared__ float l_lds[ST];
+  __shared__ float d_lds[ST];
   __shared__ unsigned short p_lds[BBLOCK / WAVE][16 * KPAD];
 
   // K/V A-fragments for this wave's 16 keys, resident for the whole kernel
@@ -138,28 +156,28 @@ __global__ __launch_bounds__(BBLOCK, 2) void flash_bwd_dkv_kernel(
 
   for (int hq = hkv * rep; hq < (hkv + 1) * rep; ++hq) {
     const float slope = ALIBI ? alibi_slopes[hq] : 0.f;  // per QUERY head
-    for (int qt = kt; qt < T; qt += BT) {  // causal: q-tiles at/after the diagonal
+    for (int qt = kt; qt < T; qt += ST) {  // causal: q-tiles at/after the diagonal
       __syncthreads();
-      stage_tileT<D>(q + ((size_t)b * Hq + hq) * (size_t)T * D, qt, T - qt, qT_lds, scale);
-      stage_tileT<D>(dout + ((size_t)b * Hq + hq) * (size_t)T * D, qt, T - qt, doT_lds, 1.f);
-      for (int i = threadIdx.x; i < BT; i += BBLOCK) {
+      stage_tileT<D, ST>(q + ((size_t)b * Hq + hq) * (size_t)T * D, qt, T - qt, qT_lds, scale);
+      stage_tileT<D, ST>(dout + ((size_t)b * Hq + hq) * (size_t)T * D, qt, T - qt, doT_lds, 1.f);
+      for (int i = threadIdx.x; i < ST; i += BBLOCK) {
         const int qrow = min(qt + i, T - 1);
         l_lds[i] = lse[((size_t)b * Hq + hq) * T + qrow];
         d_lds[i] = drow[((size_t)b * Hq + hq) * T + qrow];
       }
       __syncthreads();
 
-      // S^T / dP^T fragments [this wave's 16 keys x 64 queries]
-      f32x4_fb pt[BT / 16], dst[BT / 16];
+      // S^T / dP^T fragments [this wave's 16 keys x ST queries]
+      f32x4_fb pt[ST / 16], dst[ST / 16];
 #pragma unroll
-      for (int qq = 0; qq < BT / 16; ++qq) {
+      for (int qq = 0; qq < ST / 16; ++qq) {
         f32x4_fb st = {0.f, 0.f, 0.f, 0.f};
         f32x4_fb dpt = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int dch = 0; dch < D / 32; ++dch) {
-          bf16x8_fb qf = load_bfragT(qT_lds, qq * 16 + c, dch, g8);
+          bf16x8_fb qf = load_bfragT<KPAD>(qT_lds, qq * 16 + c, dch, g8);
           st = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k_frag[dch], qf, st, 0, 0, 0);
-          bf16x8_fb df = load_bfragT(doT_lds, qq * 16 + c, dch, g8);
+          bf16x8_fb df = load_bfragT<KPAD>(doT_lds, qq * 16 + c, dch, g8);
           dpt = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v_frag[dch], df, dpt, 0, 0, 0);
         }
         // element r: key = kt + krow0 + (lane>>4)*4 + r, query = qt + qq*16 + c
@@ -183,14 +201,14 @@ __global__ __launch_bounds__(BBLOCK, 2) void flash_bwd_dkv_kernel(
       unsigned short* pw = p_lds[wid];  // wave-private: no block barrier needed
       // dV += P^T dO  (A = P^T via relayout, B = doT natural rows = d)
 #pragma unroll
-      for (int qq = 0; qq < BT / 16; ++qq)
+      for (int qq = 0; qq < ST / 16; ++qq)
 #pragma unroll
         for (int r = 0; r < 4; ++r)
           pw[((lane >> 4) * 4 + r) * KPAD + qq * 16 + c] = f2bf(pt[qq][r]);
 #pragma unroll
       for (int d = 0; d < D / 16; ++d)
 #pragma unroll
-        for (int qch = 0; qch < BT; qch += 32) {
+        for (int qch = 0; qch < ST; qch += 32) {
           bf16x8_fb pf = *reinterpret_cast<const bf16x8_fb*>(&pw[c * KPAD + qch + g8]);
           bf16x8_fb dof =
               *reinterpret_cast<const bf16x8_fb*>(&doT_lds[(d * 16 + c) * KPAD + qch + g8]);
@@ -198,14 +216,14 @@ __global__ __launch_bounds__(BBLOCK, 2) void flash_bwd_dkv_kernel(
         }
       // dK += dS^T (scale*Q)  (A = dS^T via relayout, B = qT natural)
 #pragma unroll
-      for (int qq = 0; qq < BT / 16; ++qq)
+      for (int qq = 0; qq < ST / 16; ++qq)
 #pragma unroll
         for (int r = 0; r < 4; ++r)
           pw[((lane >> 4) * 4 + r) * KPAD + qq * 16 + c] = f2bf(dst[qq][r]);
 #pragma unroll
       for (int d = 0; d < D / 16; ++d)
 #pragma unroll
-        for (int qch = 0; qch < BT; qch += 32) {
+        for (int qch = 0; qch < ST; qch += 32) {
           bf16x8_fb sf = *reinterpret_cast<const bf16x8_fb*>(&pw[c * KPAD + qch + g8]);
           bf16x8_fb qtf =
               *reinterpret_cast<const bf16x8_fb*>(&qT_lds[(d * 16 + c) * KPAD + qch + g8]);
@@ -233,6 +251,8 @@ __global__ __launch_bounds__(BBLOCK, 2) void flash_bwd_dq_kernel(
     const float* __restrict__ drow, const int* __restrict__ key_starts,
     const float* __restrict__ alibi_slopes /* [Hq]; read iff ALIBI */,
     bf16_t* __restrict__ dq, int B, int Hq, int Hkv, int T, float scale) {
+  constexpr int ST = bwd_st(D);  // keys staged per step
+  constexpr int KPAD = ST + 8;
   const int qt = blockIdx.x * BT;
   const int h = blockIdx.y;
   const int b = blockIdx.z;
@@ -269,24 +289,24 @@ __global__ __launch_bounds__(BBLOCK, 2) void flash_bwd_dq_kernel(
 #pragma unroll
   for (int d = 0; d < D / 16; ++d) dq_acc[d] = {0.f, 0.f, 0.f, 0.f};
 
-  const int kt_lo = (kstart / BT) * BT;
+  const int kt_lo = (kstart / ST) * ST;
   const int kt_hi = min(T, qt + BT);  // causal: no key tile past this block's last query
-  for (int kt = kt_lo; kt < kt_hi; kt += BT) {
+  for (int kt = kt_lo; kt < kt_hi; kt += ST) {
     __syncthreads();
-    stage_tileT<D>(k + ((size_t)b * Hkv + hkv) * (size_t)T * D, kt, T - kt, kT_lds, 1.f);
-    stage_tileT<D>(v + ((size_t)b * Hkv + hkv) * (size_t)T * D, kt, T - kt, vT_lds, 1.f);
+    stage_tileT<D, ST>(k + ((size_t)b * Hkv + hkv) * (size_t)T * D, kt, T - kt, kT_lds, 1.f);
+    stage_tileT<D, ST>(v + ((size_t)b * Hkv + hkv) * (size_t)T * D, kt, T - kt, vT_lds, 1.f);
     __syncthreads();
 
     unsigned short* pw = p_lds[wid];
 #pragma unroll
-    for (int kk = 0; kk < BT / 16; ++kk) {
+    for (int kk = 0; kk < ST / 16; ++kk) {
       f32x4_fb s = {0.f, 0.f, 0.f, 0.f};
       f32x4_fb dp = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int dch = 0; dch < D / 32; ++dch) {
-        bf16x8_fb kf = load_bfragT(kT_lds, kk * 16 + c, dch, g8);
+        bf16x8_fb kf = load_bfragT<KPAD>(kT_lds, kk * 16 + c, dch, g8);
         s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(q_frag[dch], kf, s, 0, 0, 0);
-        bf16x8_fb vf = load_bfragT(vT_lds, kk * 16 + c, dch, g8);
+        bf16x8_fb vf = load_bfragT<KPAD>(vT_lds, kk * 16 + c, dch, g8);
         dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(do_frag[dch], vf, dp, 0, 0, 0);
       }
       // element r: query = qt + qrow0 + (lane>>4)*4 + r, key = kt + kk*16 + c
@@ -307,7 +327,7 @@ __global__ __launch_bounds__(BBLOCK, 2) void flash_bwd_dq_kernel(
 #pragma unroll
     for (int d = 0; d < D / 16; ++d)
 #pragma unroll
-      for (int kch = 0; kch < BT; kch += 32) {
+      for (int kch = 0; kch < ST; kch += 32) {
         bf16x8_fb sf = *reinterpret_cast<const bf16x8_fb*>(&pw[c * KPAD + kch + g8]);
         bf16x8_fb ktf =
             *reinterpret_cast<const bf16x8_fb*>(&kT_lds[(d * 16 + c) * KPAD + kch + g8]);
@@ -378,10 +398,16 @@ std::vector<at::Tensor> flash_prefill_bwd(const at::Tensor& q, const at::Tensor&
     case 64:
       if (sl != nullptr) LAUNCH_BWD(64, true); else LAUNCH_BWD(64, false);
       break;
+    case 96:
+      if (sl != nullptr) LAUNCH_BWD(96, true); else LAUNCH_BWD(96, false);
+      break;
     case 128:
       if (sl != nullptr) LAUNCH_BWD(128, true); else LAUNCH_BWD(128, false);
       break;
-    default: TORCH_CHECK(false, "flash_prefill_bwd: head dim must be 64 or 128");
+    case 256:
+      if (sl != nullptr) LAUNCH_BWD(256, true); else LAUNCH_BWD(256, false);
+      break;
+    default: TORCH_CHECK(false, "flash_prefill_bwd: head dim must be 64, 96, 128 or 256");
   }
 #undef LAUNCH_BWD
   HIP_CHECK_LAST();

@@ -21,9 +21,21 @@
 // ALiBi (Bloom): optional per-query-head slopes add slope[hq] * (j - key_start[b])
 // to the scaled score fragments right after the QK^T MFMA, in fp32, so the
 // row max / logsumexp include the bias (common.h alibi_score).
-// GQA maps hq -> hkv = hq / (Hq/Hkv).  Backward stays on the materializing
-// path (training attention backward is a later item; the experience forward
-// and prefill are no_grad and dominate PPO's attention time).
+// GQA maps hq -> hkv = hq / (Hq/Hkv).  The backward is csrc/flash_backward.hip.
+//
+// Head dims: 64, 96, 128, 256.  D=96 (NeoX-20B) is the same plan (D/32 = 3
+// MFMA k-steps, D/8 = 12 vectors per row: every index below divides, none
+// shifts or masks; ~50 KB LDS).  D=256 (GPT-J) does not fit that plan
+// (q+k+vt+p = 113,664 B against the 64 KB static limit), so it keeps the
+// wave's 16 query rows as register-resident A-fragments (8 bf16x8, 32 VGPRs,
+// like flash_backward.hip's load_afrag) and narrows the key tile to 32:
+// k 16.9 KB + vt 20.5 KB + p 5 KB = 42.5 KB static, two blocks per CU as at
+// the other head dims.  The alternative (64x64 tiles in >64 KB opt-in dynamic
+// LDS, one block per CU) was not built, so the choice rests on the LDS
+// arithmetic (twice the resident waves, no per-instantiation function
+// attribute), not on an A/B.  profiles/headdim_notes.md has the numbers for
+// the plan chosen: at T=1024 it is 2.4x slower than rocBLAS + causal_softmax,
+// so models do not take it by default (ops.flash_enabled).
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
 
@@ -34,7 +46,8 @@ namespace {
 constexpr int FBLOCK = 256;
 constexpr int FWAVES = FBLOCK / WAVE;
 constexpr int TQ = 64;  // queries per block (16 per wave)
-constexpr int TK = 64;  // keys per tile
+// keys per tile: 64, narrowed to 32 at D=256 (see the head-dim plans above)
+constexpr int fwd_tk(int D) { return D > 128 ? 32 : 64; }
 
 typedef __attribute__((ext_vector_type(8))) short bf16x8_fp;
 typedef __attribute__((ext_vector_type(4))) float f32x4_fp;
@@ -50,6 +63,8 @@ __global__ __launch_bounds__(FBLOCK, 2) void flash_prefill_kernel(
     float* __restrict__ lse /* [B,Hq,T] logsumexp of the SCALED (+biased) scores; may be null */,
     int B, int Hq, int Hkv, int T, int Tk,
     int Sk /* allocated token stride of k/v (cache prefill) */, int start_pos, float scale) {
+  constexpr int TK = fwd_tk(D);
+  constexpr bool QREG = D > 128;  // Q as register-resident A-fragments, not LDS
   constexpr int DPAD = D + 8;    // LDS row stride (shorts), bank-staggered
   constexpr int KPAD = TK + 8;
 
@@ -65,13 +80,27 @@ __global__ __launch_bounds__(FBLOCK, 2) void flash_prefill_kernel(
   const int lane = threadIdx.x % WAVE;
   const int wid = threadIdx.x / WAVE;
 
-  __shared__ unsigned short q_lds[TQ * DPAD];
+  __shared__ unsigned short q_lds[QREG ? 8 : TQ * DPAD];
   __shared__ unsigned short k_lds[TK * DPAD];
   __shared__ unsigned short vt_lds[D * KPAD];  // V transposed [d][key]
   __shared__ unsigned short p_lds[FWAVES][16 * KPAD];
 
   // ---- stage Q tile (pre-scaled) --------------------------------------------
-  {
+  // QREG: this wave's 16 rows x full D straight into A-fragments (row = lane&15,
+  // k-slice = (lane>>4)*8), rows clamped to the ABSOLUTE last row T-1 like
+  // flash_backward.hip's load_afrag, so no lane reads past the tensor.
+  bf16x8_fp q_frag[QREG ? D / 32 : 1];
+  if constexpr (QREG) {
+    const int qrow = min(q0 + wid * 16 + (lane & 15), T - 1);
+    const bf16_t* qp = q + (((size_t)b * Hq + h) * T + qrow) * D + (lane >> 4) * 8;
+#pragma unroll
+    for (int dch = 0; dch < D / 32; ++dch) {
+      float vals[8];
+      load8<bf16_t>(qp + dch * 32, vals);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) q_frag[dch][j] = (short)f2bf(vals[j] * scale);
+    }
+  } else {
     const bf16_t* qp = q + (((size_t)b * Hq + h) * T) * D;
     for (int i = threadIdx.x; i < TQ * (D / 8); i += FBLOCK) {
       const int row = i / (D / 8);
@@ -133,7 +162,9 @@ __global__ __launch_bounds__(FBLOCK, 2) void flash_prefill_kernel(
       f32x4_fp acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int d = 0; d < D; d += 32) {
-        bf16x8_fp af = *reinterpret_cast<const bf16x8_fp*>(&q_lds[(qrow0 + c) * DPAD + d + g8]);
+        bf16x8_fp af;
+        if constexpr (QREG) af = q_frag[d / 32];
+        else af = *reinterpret_cast<const bf16x8_fp*>(&q_lds[(qrow0 + c) * DPAD + d + g8]);
         bf16x8_fp bf = *reinterpret_cast<const bf16x8_fp*>(&k_lds[(kk * 16 + c) * DPAD + d + g8]);
         acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bf, acc, 0, 0, 0);
       }
@@ -297,11 +328,17 @@ std::vector<at::Tensor> flash_prefill_lse(const at::Tensor& q, const at::Tensor&
     case 64:
       if (sl != nullptr) LAUNCH_FWD(64, true); else LAUNCH_FWD(64, false);
       break;
+    case 96:
+      if (sl != nullptr) LAUNCH_FWD(96, true); else LAUNCH_FWD(96, false);
+      break;
     case 128:
       if (sl != nullptr) LAUNCH_FWD(128, true); else LAUNCH_FWD(128, false);
       break;
+    case 256:
+      if (sl != nullptr) LAUNCH_FWD(256, true); else LAUNCH_FWD(256, false);
+      break;
     default:
-      TORCH_CHECK(false, "flash_prefill: head dim must be 64 or 128, got ", D);
+      TORCH_CHECK(false, "flash_prefill: head dim must be 64, 96, 128 or 256, got ", D);
   }
 #undef LAUNCH_FWD
   HIP_CHECK_LAST();

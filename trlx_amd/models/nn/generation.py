@@ -447,7 +447,7 @@ def generate(
         # the graph engine needs the fused decode kernels (device-side cache
         # index); unsupported head dims use the eager loop's host-side state.
         # ALiBi models qualify: the decode kernels take the head slopes.
-        head_ok = getattr(model.config, "head_dim", 64) in (32, 64, 128, 256)
+        head_ok = getattr(model.config, "head_dim", 64) in ops.DECODE_HEAD_DIMS
         if (device.type == "cuda" and shaping_graphable and gen.use_graph
                 and head_ok and not has_virtual
                 and _graphs_enabled() and gen.max_new_tokens > 1 and gen.min_new_tokens == 0):

@@ -19,7 +19,6 @@ Design points:
 """
 
 import math
-import os
 from dataclasses import dataclass
 from typing import List, Optional, Tuple
 
@@ -183,7 +182,7 @@ class Attention(nn.Module):
         # append) + flash-decode attention, fully device-side (hipGraph-safe)
         if (T == 1 and kv_cache is not None and ctx.cache_idx is not None
                 and ctx.seq_lens is not None and x.is_cuda
-                and self.head_dim in (32, 64, 128, 256)):
+                and self.head_dim in ops.DECODE_HEAD_DIMS):
             # (unsupported head dims fall through to the eager T=1 math below)
             cos_sin = rope_tables if self.cfg.position_encoding == "rope" else (None, None)
             if self.num_heads == self.num_kv_heads:
@@ -242,11 +241,11 @@ class Attention(nn.Module):
 
         flash_ok = (
             T > 1 and x.is_cuda and q.dtype == torch.bfloat16
-            and self.head_dim in (64, 128)
             and not torch.is_grad_enabled()
             and (self.attn_pdrop == 0 or not self.training)
             and ops.extension_available()
-            and os.environ.get("TRLX_AMD_NO_FLASH_PREFILL") != "1"
+            # head dim + TRLX_AMD_NO_FLASH_PREFILL, per the measured defaults
+            and ops.flash_enabled(self.head_dim, train=False)
         )
         if kv_cache is not None:
             if pre_scaled:
@@ -257,7 +256,7 @@ class Attention(nn.Module):
             else:
                 k_full, v_full = kv_cache.update(self.layer_idx, k, v, ctx.start_pos)
             if (T == 1 and ctx.seq_lens is not None
-                    and (not x.is_cuda or self.head_dim in (32, 64, 128, 256))):
+                    and (not x.is_cuda or self.head_dim in ops.DECODE_HEAD_DIMS)):
                 # fused flash-decode kernel (qkv_prep may already have scaled
                 # q: passing self.scale again double-scaled the PP/direct
                 # decode path on GPU — caught by the ctx-level decode test)
@@ -290,12 +289,11 @@ class Attention(nn.Module):
 
         flash_train_ok = (
             T > 1 and x.is_cuda and q.dtype == torch.bfloat16
-            and self.head_dim in (64, 128)
             and torch.is_grad_enabled() and kv_cache is None and ctx.start_pos == 0
             and (self.attn_pdrop == 0 or not self.training)
             and ops.extension_available()
-            and os.environ.get("TRLX_AMD_NO_FLASH_PREFILL") != "1"
-            and os.environ.get("TRLX_AMD_NO_FLASH_TRAIN") != "1"
+            # head dim + TRLX_AMD_NO_FLASH_PREFILL / TRLX_AMD_NO_FLASH_TRAIN
+            and ops.flash_enabled(self.head_dim, train=True)
         )
         if flash_train_ok:
             # TRAINING forward: differentiable flash attention — forward saves

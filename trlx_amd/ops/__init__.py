@@ -16,6 +16,44 @@ import torch
 
 from . import reference
 
+# Head dims the attention kernels are instantiated for — the one source of
+# truth for every dispatch gate (models/nn/transformer.py, generation.py); the
+# switch (D) blocks in csrc/flash_prefill.hip, flash_backward.hip and
+# attn_decode.hip list the same sets.
+FLASH_HEAD_DIMS = (64, 96, 128, 256)  # flash_prefill / flash_attention (fwd + bwd)
+DECODE_HEAD_DIMS = (32, 64, 96, 128, 256)  # attention_decode / fused_decode_attention
+
+# Which of FLASH_HEAD_DIMS the model takes BY DEFAULT, per direction.  The
+# project's rule: a fusion is the default only where a same-box A/B against
+# the materializing rocBLAS + causal_softmax path shows it not slower
+# (profiles/headdim_notes.md).  D=96 wins the no_grad forward and loses the
+# training forward+backward; D=256 loses both.  The losing (D, direction)
+# pairs stay reachable — they are the O(T) memory path — by setting the
+# existing switch to 0: TRLX_AMD_NO_FLASH_PREFILL=0 / TRLX_AMD_NO_FLASH_TRAIN=0.
+FLASH_PREFILL_DEFAULT_DIMS = (64, 96, 128)
+FLASH_TRAIN_DEFAULT_DIMS = (64, 128)
+
+
+def flash_enabled(head_dim: int, train: bool) -> bool:
+    """Does a model with this head dim take the flash kernels for the no_grad
+    forward (``train=False``) or the training forward+backward (``train=True``)?
+
+    ``TRLX_AMD_NO_FLASH_PREFILL=1`` turns both directions off and
+    ``TRLX_AMD_NO_FLASH_TRAIN=1`` the training direction; ``=0`` turns the
+    direction on for every instantiated head dim; unset follows the measured
+    defaults above."""
+    if head_dim not in FLASH_HEAD_DIMS:
+        return False
+    prefill = os.environ.get("TRLX_AMD_NO_FLASH_PREFILL")
+    if prefill == "1":
+        return False
+    if not train:
+        return prefill == "0" or head_dim in FLASH_PREFILL_DEFAULT_DIMS
+    switch = os.environ.get("TRLX_AMD_NO_FLASH_TRAIN")
+    if switch == "1":
+        return False
+    return switch == "0" or head_dim in FLASH_TRAIN_DEFAULT_DIMS
+
 _EXT = None
 _EXT_TRIED = False
 _EXT_ERR: Optional[str] = None
