@@ -105,19 +105,25 @@ void stage_gemm_v3(const at::Tensor& a, const at::Tensor& w, const c10::optional
 at::Tensor flash_prefill(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
                          const c10::optional<at::Tensor>& key_starts, long start_pos,
                          double scale, long tk,
-                         const c10::optional<at::Tensor>& alibi_slopes);
+                         const c10::optional<at::Tensor>& alibi_slopes,
+                         const c10::optional<at::Tensor>& rel_bias, long bias_zero,
+                         const c10::optional<at::Tensor>& key_mask, bool causal);
 std::vector<at::Tensor> flash_prefill_lse(const at::Tensor& q, const at::Tensor& k,
                                           const at::Tensor& v,
                                           const c10::optional<at::Tensor>& key_starts,
                                           long start_pos, double scale, long tk,
                                           bool want_lse,
-                                          const c10::optional<at::Tensor>& alibi_slopes);
+                                          const c10::optional<at::Tensor>& alibi_slopes,
+                                          const c10::optional<at::Tensor>& rel_bias, long bias_zero,
+                                          const c10::optional<at::Tensor>& key_mask, bool causal);
 std::vector<at::Tensor> flash_prefill_bwd(const at::Tensor& q, const at::Tensor& k,
                                           const at::Tensor& v, const at::Tensor& out,
                                           const at::Tensor& dout, const at::Tensor& lse,
                                           const c10::optional<at::Tensor>& key_starts,
                                           double scale,
-                                          const c10::optional<at::Tensor>& alibi_slopes);
+                                          const c10::optional<at::Tensor>& alibi_slopes,
+                                          const c10::optional<at::Tensor>& rel_bias, long bias_zero,
+                                          const c10::optional<at::Tensor>& key_mask, bool causal);
 void lm_sample_v3(const at::Tensor& x, const at::Tensor& wlm,
                   const c10::optional<at::Tensor>& blm, const at::Tensor& pstats, long nparts,
                   const at::Tensor& nw, const c10::optional<at::Tensor>& nb, at::Tensor& packed,
@@ -169,14 +175,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("lm_sample_v2", &lm_sample_v2);
   mod.def("stage_gemm_v3", &stage_gemm_v3);
   mod.def("lm_sample_v3", &lm_sample_v3);
-  // trailing alibi_slopes defaults to None: positional callers keep working
+  // trailing alibi_slopes and the seq2seq (T5) arguments rel_bias / bias_zero /
+  // key_mask / causal take defaults: positional callers keep working
   mod.def("flash_prefill", &flash_prefill, py::arg("q"), py::arg("k"), py::arg("v"),
           py::arg("key_starts"), py::arg("start_pos"), py::arg("scale"), py::arg("tk"),
-          py::arg("alibi_slopes") = py::none());
+          py::arg("alibi_slopes") = py::none(),
+          py::arg("rel_bias") = py::none(), py::arg("bias_zero") = 0,
+          py::arg("key_mask") = py::none(), py::arg("causal") = true);
   mod.def("flash_prefill_lse", &flash_prefill_lse, py::arg("q"), py::arg("k"), py::arg("v"),
           py::arg("key_starts"), py::arg("start_pos"), py::arg("scale"), py::arg("tk"),
-          py::arg("want_lse"), py::arg("alibi_slopes") = py::none());
+          py::arg("want_lse"), py::arg("alibi_slopes") = py::none(),
+          py::arg("rel_bias") = py::none(), py::arg("bias_zero") = 0,
+          py::arg("key_mask") = py::none(), py::arg("causal") = true);
   mod.def("flash_prefill_bwd", &flash_prefill_bwd, py::arg("q"), py::arg("k"), py::arg("v"),
           py::arg("out"), py::arg("dout"), py::arg("lse"), py::arg("key_starts"),
-          py::arg("scale"), py::arg("alibi_slopes") = py::none());
+          py::arg("scale"), py::arg("alibi_slopes") = py::none(),
+          py::arg("rel_bias") = py::none(), py::arg("bias_zero") = 0,
+          py::arg("key_mask") = py::none(), py::arg("causal") = true);
 }

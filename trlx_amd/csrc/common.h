@@ -184,6 +184,43 @@ DEV float alibi_score(float score, float slope, int key, int kstart) {
   return __builtin_fmaf(slope, (float)(key - kstart), score);
 }
 
+// ---- T5 relative-position bias ------------------------------------------------
+
+// scaled score + bias_row[key - qpos + bias_zero] in fp32.  The T5 bias depends
+// on key - query position only, so one head's [Tq, Tk] bias is a Toeplitz
+// vector bias_row[0..L) with relative position 0 at index bias_zero
+// (ops.t5_rel_bias).  The flash forward and both flash backward kernels call
+// this one helper, so the backward's recomputed P matches the saved logsumexp.
+// Lanes that stand for rows >= Tq or keys >= Tk (masked later) compute an
+// index outside [0, L): the index is clamped BEFORE the load, never after.
+DEV float rel_bias_score(float score, const float* __restrict__ bias_row, int L, int key,
+                         int qpos, int bias_zero) {
+  const int idx = min(max(key - qpos + bias_zero, 0), L - 1);
+  return score + bias_row[idx];
+}
+
+// The seq2seq kernel arguments travel as a trailing parameter PACK: the causal
+// instantiations have an empty pack and so exactly the argument list (and
+// kernarg segment, which steers how the compiler merges the scalar argument
+// loads) they had before these modes existed.
+struct S2SView {
+  const float* rel_bias;          // [Hq, bias_len]
+  int bias_len, bias_zero;
+  const unsigned char* key_mask;  // [B, Tk]
+  int Tk;                         // backward only: keys when Tq != Tk
+};
+// A kernel checks its pack with s2s_pack_ok: empty exactly when no seq2seq flag
+// is set, otherwise the 4 (forward) or 5 (backward) arguments below, so a
+// mismatched launch is a compile error and never a silently null view.
+constexpr bool s2s_pack_ok(bool any_flag, int pack_size, int expected) {
+  return any_flag ? pack_size == expected : pack_size == 0;
+}
+DEV S2SView s2s_view() { return {nullptr, 0, 0, nullptr, 0}; }
+DEV S2SView s2s_view(const float* rel_bias, int bias_len, int bias_zero,
+                     const unsigned char* key_mask, int Tk = 0) {
+  return {rel_bias, bias_len, bias_zero, key_mask, Tk};
+}
+
 // ---- counter-based RNG (splitmix64) -----------------------------------------
 
 DEV unsigned long long splitmix64(unsigned long long z) {
@@ -222,7 +259,60 @@ inline const float* alibi_slopes_ptr(const c10::optional<at::Tensor>& slopes,
   return slopes->data_ptr<float>();
 }
 
-#define HIP_CHECK_LAST()                                           \
+// host side: the seq2seq (T5) modes of the flash kernels — non-causal,
+// Toeplitz relative bias, arbitrary key mask.  Validates the optional inputs
+// and returns raw pointers (null = mode off).  `any` says whether a seq2seq
+// instantiation is needed at all; those exist at head dims 64 and 128 only.
+struct Seq2SeqArgs {
+  const float* rel_bias = nullptr;  // [Hq, L] fp32
+  int bias_len = 0;                 // L
+  int bias_zero = 0;                // index of relative position 0
+  const unsigned char* key_mask = nullptr;  // [B, Tk], nonzero = visible
+  bool any = false;
+};
+
+inline Seq2SeqArgs seq2seq_args(const c10::optional<at::Tensor>& rel_bias, long bias_zero,
+                                const c10::optional<at::Tensor>& key_mask, bool causal,
+                                bool has_key_starts, bool has_alibi, const at::Tensor& like,
+                                long B, long num_q_heads, long Tq, long Tk, long start_pos,
+                                long D, const char* op) {
+  Seq2SeqArgs a;
+  if (rel_bias.has_value()) {
+    TORCH_CHECK(!has_alibi, op, ": rel_bias and alibi_slopes are mutually exclusive");
+    TORCH_CHECK(rel_bias->dtype() == at::kFloat && rel_bias->is_contiguous() &&
+                    rel_bias->dim() == 2 && rel_bias->size(0) == num_q_heads,
+                op, ": rel_bias must be contiguous fp32 [Hq, L]");
+    TORCH_CHECK(rel_bias->device() == like.device(), op,
+                ": rel_bias must live on the same device as the inputs");
+    const long L = rel_bias->size(1);
+    TORCH_CHECK(bias_zero - (start_pos + Tq - 1) >= 0 && bias_zero + Tk - 1 < L, op,
+                ": rel_bias [Hq, ", L, "] with bias_zero ", bias_zero,
+                " does not cover queries ", start_pos, "..", start_pos + Tq - 1, " x keys 0..",
+                Tk - 1);
+    a.rel_bias = rel_bias->data_ptr<float>();
+    a.bias_len = (int)L;
+    a.bias_zero = (int)bias_zero;
+  }
+  if (key_mask.has_value()) {
+    TORCH_CHECK(!has_key_starts, op, ": key_mask and key_starts are mutually exclusive");
+    TORCH_CHECK(key_mask->dtype() == at::kByte && key_mask->is_contiguous() &&
+                    key_mask->dim() == 2 && key_mask->size(0) == B && key_mask->size(1) == Tk,
+                op, ": key_mask must be contiguous uint8 [B, Tk]");
+    TORCH_CHECK(key_mask->device() == like.device(), op,
+                ": key_mask must live on the same device as the inputs");
+    TORCH_CHECK(Tk > 0, op, ": key_mask needs at least one key");
+    a.key_mask = key_mask->data_ptr<unsigned char>();
+  }
+  a.any = a.rel_bias != nullptr || a.key_mask != nullptr || !causal;
+  if (a.any) {
+    TORCH_CHECK(!has_alibi, op, ": key_mask / non-causal attention do not combine with alibi_slopes");
+    TORCH_CHECK(D == 64 || D == 128, op,
+                ": rel_bias / key_mask / non-causal attention need head dim 64 or 128, got ", D);
+  }
+  return a;
+}
+
+#define HIP_CHECK_LAST()                                          \
   do {                                                             \
     hipError_t e = hipGetLastError();                              \
     TORCH_CHECK(e == hipSuccess, "HIP error: ", hipGetErrorString(e)); \

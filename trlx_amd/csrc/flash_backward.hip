@@ -36,6 +36,13 @@
 // models take them only when asked (ops.flash_enabled): the O(T)-memory path.
 // Masking (causal + left-pad key_starts) matches the forward; fully-masked
 // query rows carry L = +inf so P == 0 and they contribute nothing.
+// Seq2seq (T5) modes at head dims 64 / 128 mirror the forward's: non-causal
+// (dKV sweeps every q-tile, dQ every key tile), rectangular Tq != Tk, the
+// Toeplitz relative bias and the arbitrary key mask inside the recomputed P.
+// The learned bias itself gets no gradient here.
+// Precondition (as for left-pad key_starts): K and V rows at masked keys are
+// FINITE.  A masked key enters dS as p * (dP - Drow) with p == 0, which is
+// exact for any finite K/V (the tests fill them with 1e4) and NaN for inf/NaN.
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
 
@@ -111,20 +118,35 @@ DEV bf16x8_fb load_bfragT(const unsigned short* __restrict__ tds, int col, int d
 
 // ALIBI is a template parameter in both kernels (as in the forward): the
 // no-bias instantiations compile to exactly the code they were without it.
-template <int D, bool ALIBI>
+// So are the seq2seq (T5) modes CAUSAL / RELB / KMASK (see flash_prefill.hip);
+// their kernel arguments are the trailing pack S2S, empty for the causal
+// instantiations.  Rectangular attention (Tq != Tk, cross-
+// attention) exists only with CAUSAL off: q/dout/lse/drow/dq are [.., Tq, ..]
+// and k/v/dk/dv are [.., Tk, ..].  Causal training keeps Tq == Tk (checked on
+// the host), and the causal instantiations keep using the one T for both.
+template <int D, bool ALIBI, bool CAUSAL = true, bool RELB = false, bool KMASK = false,
+          typename... S2S>
 __global__ __launch_bounds__(BBLOCK, dkv_waves(D)) void flash_bwd_dkv_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
     const bf16_t* __restrict__ dout, const float* __restrict__ lse,
     const float* __restrict__ drow, const int* __restrict__ key_starts,
     const float* __restrict__ alibi_slopes /* [Hq]; read iff ALIBI */,
-    bf16_t* __restrict__ dk, bf16_t* __restrict__ dv, int B, int Hq, int Hkv, int T,
-    float scale) {
+    bf16_t* __restrict__ dk, bf16_t* __restrict__ dv, int B, int Hq, int Hkv,
+    int Tq /* queries; also the keys when CAUSAL */, float scale,
+    S2S... s2s_args /* rel_bias, bias_len, bias_zero, key_mask, Tk (common.h s2s_view) */) {
+  static_assert(s2s_pack_ok(!CAUSAL || RELB || KMASK, sizeof...(S2S), 5),
+                "seq2seq arguments: (rel_bias, bias_len, bias_zero, key_mask, Tk) iff a mode is on");
+  const S2SView s2s = s2s_view(s2s_args...);
+  const float* __restrict__ rel_bias = s2s.rel_bias;          // read iff RELB
+  const unsigned char* __restrict__ key_mask = s2s.key_mask;  // read iff KMASK
+  const int bias_len = s2s.bias_len, bias_zero = s2s.bias_zero;
   constexpr int ST = bwd_st(D);  // queries staged per step
   constexpr int KPAD = ST + 8;
+  const int Tk = CAUSAL ? Tq : s2s.Tk;
   const int kt = blockIdx.x * BT;
   const int hkv = blockIdx.y;
   const int b = blockIdx.z;
-  if (kt >= T) return;
+  if (kt >= Tk) return;
   const int rep = Hq / Hkv;
   const int kstart = key_starts ? key_starts[b] : 0;
 
@@ -142,10 +164,18 @@ __global__ __launch_bounds__(BBLOCK, dkv_waves(D)) void flash_bwd_dkv_kernel(
 
   // K/V A-fragments for this wave's 16 keys, resident for the whole kernel
   bf16x8_fb k_frag[D / 32], v_frag[D / 32];
-  load_afrag<D>(k + ((size_t)b * Hkv + hkv) * (size_t)T * D, kt + krow0, (long)T - 1, lane,
+  load_afrag<D>(k + ((size_t)b * Hkv + hkv) * (size_t)Tk * D, kt + krow0, (long)Tk - 1, lane,
                 k_frag, 1.f);
-  load_afrag<D>(v + ((size_t)b * Hkv + hkv) * (size_t)T * D, kt + krow0, (long)T - 1, lane,
+  load_afrag<D>(v + ((size_t)b * Hkv + hkv) * (size_t)Tk * D, kt + krow0, (long)Tk - 1, lane,
                 v_frag, 1.f);
+  // this lane's 4 keys are fixed for the whole kernel: read their mask once
+  // (index clamped to the last key; keys >= Tk are masked by `key < Tk`)
+  bool kvis[4] = {true, true, true, true};
+  if constexpr (KMASK) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      kvis[r] = key_mask[(size_t)b * Tk + min(kt + krow0 + (lane >> 4) * 4 + r, Tk - 1)] != 0;
+  }
 
   f32x4_fb dv_acc[D / 16], dk_acc[D / 16];
 #pragma unroll
@@ -156,14 +186,16 @@ __global__ __launch_bounds__(BBLOCK, dkv_waves(D)) void flash_bwd_dkv_kernel(
 
   for (int hq = hkv * rep; hq < (hkv + 1) * rep; ++hq) {
     const float slope = ALIBI ? alibi_slopes[hq] : 0.f;  // per QUERY head
-    for (int qt = kt; qt < T; qt += ST) {  // causal: q-tiles at/after the diagonal
+    // causal: q-tiles at/after the diagonal; otherwise every q-tile
+    for (int qt = CAUSAL ? kt : 0; qt < Tq; qt += ST) {
       __syncthreads();
-      stage_tileT<D, ST>(q + ((size_t)b * Hq + hq) * (size_t)T * D, qt, T - qt, qT_lds, scale);
-      stage_tileT<D, ST>(dout + ((size_t)b * Hq + hq) * (size_t)T * D, qt, T - qt, doT_lds, 1.f);
+      stage_tileT<D, ST>(q + ((size_t)b * Hq + hq) * (size_t)Tq * D, qt, Tq - qt, qT_lds, scale);
+      stage_tileT<D, ST>(dout + ((size_t)b * Hq + hq) * (size_t)Tq * D, qt, Tq - qt, doT_lds,
+                         1.f);
       for (int i = threadIdx.x; i < ST; i += BBLOCK) {
-        const int qrow = min(qt + i, T - 1);
-        l_lds[i] = lse[((size_t)b * Hq + hq) * T + qrow];
-        d_lds[i] = drow[((size_t)b * Hq + hq) * T + qrow];
+        const int qrow = min(qt + i, Tq - 1);
+        l_lds[i] = lse[((size_t)b * Hq + hq) * Tq + qrow];
+        d_lds[i] = drow[((size_t)b * Hq + hq) * Tq + qrow];
       }
       __syncthreads();
 
@@ -187,9 +219,13 @@ __global__ __launch_bounds__(BBLOCK, dkv_waves(D)) void flash_bwd_dkv_kernel(
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int key = kt + krow0 + (lane >> 4) * 4 + r;
-          const bool valid = key < T && key >= kstart && key <= qpos && qpos < T;
+          const bool valid = key < Tk && key >= kstart && (!CAUSAL || key <= qpos) &&
+                             qpos < Tq && kvis[r];
           // same biased score the forward folded into L
           if constexpr (ALIBI) st[r] = alibi_score(st[r], slope, key, kstart);
+          if constexpr (RELB)
+            st[r] = rel_bias_score(st[r], rel_bias + (size_t)hq * bias_len, bias_len, key, qpos,
+                                   bias_zero);
           const float p = (valid && L < INFINITY) ? __expf(st[r] - L) : 0.f;
           st[r] = p;
           dpt[r] = p * (dpt[r] - Dr);
@@ -238,25 +274,35 @@ __global__ __launch_bounds__(BBLOCK, dkv_waves(D)) void flash_bwd_dkv_kernel(
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int key = kt + krow0 + (lane >> 4) * 4 + r;
-      if (key >= T) continue;
-      dv[(((size_t)b * Hkv + hkv) * T + key) * D + d * 16 + c].u = f2bf(dv_acc[d][r]);
-      dk[(((size_t)b * Hkv + hkv) * T + key) * D + d * 16 + c].u = f2bf(dk_acc[d][r]);
+      if (key >= Tk) continue;
+      dv[(((size_t)b * Hkv + hkv) * Tk + key) * D + d * 16 + c].u = f2bf(dv_acc[d][r]);
+      dk[(((size_t)b * Hkv + hkv) * Tk + key) * D + d * 16 + c].u = f2bf(dk_acc[d][r]);
     }
 }
 
-template <int D, bool ALIBI>
+template <int D, bool ALIBI, bool CAUSAL = true, bool RELB = false, bool KMASK = false,
+          typename... S2S>
 __global__ __launch_bounds__(BBLOCK, 2) void flash_bwd_dq_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
     const bf16_t* __restrict__ dout, const float* __restrict__ lse,
     const float* __restrict__ drow, const int* __restrict__ key_starts,
     const float* __restrict__ alibi_slopes /* [Hq]; read iff ALIBI */,
-    bf16_t* __restrict__ dq, int B, int Hq, int Hkv, int T, float scale) {
+    bf16_t* __restrict__ dq, int B, int Hq, int Hkv,
+    int Tq /* queries; also the keys when CAUSAL */, float scale,
+    S2S... s2s_args /* rel_bias, bias_len, bias_zero, key_mask, Tk (common.h s2s_view) */) {
+  static_assert(s2s_pack_ok(!CAUSAL || RELB || KMASK, sizeof...(S2S), 5),
+                "seq2seq arguments: (rel_bias, bias_len, bias_zero, key_mask, Tk) iff a mode is on");
+  const S2SView s2s = s2s_view(s2s_args...);
+  const float* __restrict__ rel_bias = s2s.rel_bias;          // read iff RELB
+  const unsigned char* __restrict__ key_mask = s2s.key_mask;  // read iff KMASK
+  const int bias_len = s2s.bias_len, bias_zero = s2s.bias_zero;
   constexpr int ST = bwd_st(D);  // keys staged per step
   constexpr int KPAD = ST + 8;
+  const int Tk = CAUSAL ? Tq : s2s.Tk;
   const int qt = blockIdx.x * BT;
   const int h = blockIdx.y;
   const int b = blockIdx.z;
-  if (qt >= T) return;
+  if (qt >= Tq) return;
   const int hkv = h / (Hq / Hkv);
   const int kstart = key_starts ? key_starts[b] : 0;
   const float slope = ALIBI ? alibi_slopes[h] : 0.f;
@@ -273,16 +319,16 @@ __global__ __launch_bounds__(BBLOCK, 2) void flash_bwd_dq_kernel(
 
   // scaled-Q / dO A-fragments for this wave's 16 queries, plus their L / Drow
   bf16x8_fb q_frag[D / 32], do_frag[D / 32];
-  load_afrag<D>(q + ((size_t)b * Hq + h) * (size_t)T * D, qt + qrow0, (long)T - 1, lane,
+  load_afrag<D>(q + ((size_t)b * Hq + h) * (size_t)Tq * D, qt + qrow0, (long)Tq - 1, lane,
                 q_frag, scale);
-  load_afrag<D>(dout + ((size_t)b * Hq + h) * (size_t)T * D, qt + qrow0, (long)T - 1, lane,
+  load_afrag<D>(dout + ((size_t)b * Hq + h) * (size_t)Tq * D, qt + qrow0, (long)Tq - 1, lane,
                 do_frag, 1.f);
   float L_r[4], D_r[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    const int qrow = min(qt + qrow0 + (lane >> 4) * 4 + r, T - 1);
-    L_r[r] = lse[((size_t)b * Hq + h) * T + qrow];
-    D_r[r] = drow[((size_t)b * Hq + h) * T + qrow];
+    const int qrow = min(qt + qrow0 + (lane >> 4) * 4 + r, Tq - 1);
+    L_r[r] = lse[((size_t)b * Hq + h) * Tq + qrow];
+    D_r[r] = drow[((size_t)b * Hq + h) * Tq + qrow];
   }
 
   f32x4_fb dq_acc[D / 16];
@@ -290,11 +336,12 @@ __global__ __launch_bounds__(BBLOCK, 2) void flash_bwd_dq_kernel(
   for (int d = 0; d < D / 16; ++d) dq_acc[d] = {0.f, 0.f, 0.f, 0.f};
 
   const int kt_lo = (kstart / ST) * ST;
-  const int kt_hi = min(T, qt + BT);  // causal: no key tile past this block's last query
+  // causal: no key tile past this block's last query
+  const int kt_hi = CAUSAL ? min(Tk, qt + BT) : Tk;
   for (int kt = kt_lo; kt < kt_hi; kt += ST) {
     __syncthreads();
-    stage_tileT<D, ST>(k + ((size_t)b * Hkv + hkv) * (size_t)T * D, kt, T - kt, kT_lds, 1.f);
-    stage_tileT<D, ST>(v + ((size_t)b * Hkv + hkv) * (size_t)T * D, kt, T - kt, vT_lds, 1.f);
+    stage_tileT<D, ST>(k + ((size_t)b * Hkv + hkv) * (size_t)Tk * D, kt, Tk - kt, kT_lds, 1.f);
+    stage_tileT<D, ST>(v + ((size_t)b * Hkv + hkv) * (size_t)Tk * D, kt, Tk - kt, vT_lds, 1.f);
     __syncthreads();
 
     unsigned short* pw = p_lds[wid];
@@ -311,11 +358,17 @@ __global__ __launch_bounds__(BBLOCK, 2) void flash_bwd_dq_kernel(
       }
       // element r: query = qt + qrow0 + (lane>>4)*4 + r, key = kt + kk*16 + c
       const int key = kt + kk * 16 + c;
+      bool kvis = true;  // index clamped: keys >= Tk are masked by `key < Tk` anyway
+      if constexpr (KMASK) kvis = key_mask[(size_t)b * Tk + min(key, Tk - 1)] != 0;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int qrow = qt + qrow0 + (lane >> 4) * 4 + r;
-        const bool valid = key < T && key >= kstart && key <= qrow && qrow < T;
+        const bool valid = key < Tk && key >= kstart && (!CAUSAL || key <= qrow) &&
+                           qrow < Tq && kvis;
         if constexpr (ALIBI) s[r] = alibi_score(s[r], slope, key, kstart);
+        if constexpr (RELB)
+          s[r] = rel_bias_score(s[r], rel_bias + (size_t)h * bias_len, bias_len, key, qrow,
+                                bias_zero);
         const float p = (valid && L_r[r] < INFINITY) ? __expf(s[r] - L_r[r]) : 0.f;
         s[r] = p * (dp[r] - D_r[r]);  // dS
       }
@@ -340,8 +393,8 @@ __global__ __launch_bounds__(BBLOCK, 2) void flash_bwd_dq_kernel(
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int qrow = qt + qrow0 + (lane >> 4) * 4 + r;
-      if (qrow >= T) continue;
-      dq[(((size_t)b * Hq + h) * T + qrow) * D + d * 16 + c].u = f2bf(scale * dq_acc[d][r]);
+      if (qrow >= Tq) continue;
+      dq[(((size_t)b * Hq + h) * Tq + qrow) * D + d * 16 + c].u = f2bf(scale * dq_acc[d][r]);
     }
 }
 
@@ -355,15 +408,25 @@ std::vector<at::Tensor> flash_prefill_bwd(const at::Tensor& q, const at::Tensor&
                                           const at::Tensor& dout, const at::Tensor& lse,
                                           const c10::optional<at::Tensor>& key_starts,
                                           double scale,
-                                          const c10::optional<at::Tensor>& alibi_slopes) {
+                                          const c10::optional<at::Tensor>& alibi_slopes,
+                                          const c10::optional<at::Tensor>& rel_bias,
+                                          long bias_zero,
+                                          const c10::optional<at::Tensor>& key_mask,
+                                          bool causal) {
   TORCH_CHECK(q.is_cuda() && q.dtype() == at::kBFloat16 && q.dim() == 4 && q.is_contiguous(),
               "flash_prefill_bwd: q must be contiguous bf16 [B,Hq,T,D]");
   TORCH_CHECK(k.is_contiguous() && v.is_contiguous() && lse.is_contiguous());
   const int B = q.size(0), Hq = q.size(1), T = q.size(2), D = q.size(3);
-  const int Hkv = k.size(1);
-  TORCH_CHECK(k.size(2) == T, "flash_prefill_bwd: training path only (Tk == T)");
-  TORCH_CHECK(Hq % Hkv == 0);
+  const int Hkv = k.size(1), Tk = k.size(2);
+  // causal training: full self-attention from position 0 (the kernels have no
+  // start_pos); only the non-causal modes take Tq != Tk (cross-attention)
+  TORCH_CHECK(!causal || Tk == T, "flash_prefill_bwd: training path only (Tk == T)");
+  TORCH_CHECK(Hq % Hkv == 0 && k.size(3) == D && v.sizes() == k.sizes());
+  TORCH_CHECK(out.sizes() == q.sizes() && dout.sizes() == q.sizes() && lse.numel() == (long)B * Hq * T);
   const float* sl = alibi_slopes_ptr(alibi_slopes, q, Hq, "flash_prefill_bwd");
+  const Seq2SeqArgs s2s =
+      seq2seq_args(rel_bias, bias_zero, key_mask, causal, key_starts.has_value(), sl != nullptr,
+                   q, B, Hq, T, Tk, 0, D, "flash_prefill_bwd");
   auto dq = at::empty_like(q);
   auto dk = at::empty_like(k);
   auto dv = at::empty_like(v);
@@ -383,7 +446,7 @@ std::vector<at::Tensor> flash_prefill_bwd(const at::Tensor& q, const at::Tensor&
   auto dqp = reinterpret_cast<bf16_t*>(dq.data_ptr());
   auto dkp = reinterpret_cast<bf16_t*>(dk.data_ptr());
   auto dvp = reinterpret_cast<bf16_t*>(dv.data_ptr());
-  dim3 gk((T + BT - 1) / BT, Hkv, B);
+  dim3 gk((Tk + BT - 1) / BT, Hkv, B);
   dim3 gq((T + BT - 1) / BT, Hq, B);
 #define LAUNCH_BWD(DV, AL)                                                                \
   do {                                                                                    \
@@ -394,6 +457,36 @@ std::vector<at::Tensor> flash_prefill_bwd(const at::Tensor& q, const at::Tensor&
         qp, kp, vp, dop, lse.data_ptr<float>(), drow.data_ptr<float>(), ks, sl, dqp, B,   \
         Hq, Hkv, T, (float)scale);                                                        \
   } while (0)
+#define LAUNCH_S2S(DV, CA, RB, KM)                                                        \
+  do {                                                                                    \
+    flash_bwd_dkv_kernel<DV, false, CA, RB, KM><<<gk, BBLOCK, 0, stream>>>(               \
+        qp, kp, vp, dop, lse.data_ptr<float>(), drow.data_ptr<float>(), ks, sl, dkp, dvp, \
+        B, Hq, Hkv, T, (float)scale, s2s.rel_bias, s2s.bias_len, s2s.bias_zero,           \
+        s2s.key_mask, Tk);                                                                \
+    flash_bwd_dq_kernel<DV, false, CA, RB, KM><<<gq, BBLOCK, 0, stream>>>(                \
+        qp, kp, vp, dop, lse.data_ptr<float>(), drow.data_ptr<float>(), ks, sl, dqp, B,   \
+        Hq, Hkv, T, (float)scale, s2s.rel_bias, s2s.bias_len, s2s.bias_zero,              \
+        s2s.key_mask, Tk);                                                                \
+  } while (0)
+  // seq2seq modes (head dims 64 / 128, checked in seq2seq_args): one
+  // instantiation per (causal, bias, mask) combination
+#define LAUNCH_BWD_S2S(DV)                                                                \
+  do {                                                                                    \
+    const bool rb = s2s.rel_bias != nullptr, km = s2s.key_mask != nullptr;                \
+    if (causal) {                                                                         \
+      if (rb && km) LAUNCH_S2S(DV, true, true, true);                                     \
+      else if (rb) LAUNCH_S2S(DV, true, true, false);                                     \
+      else LAUNCH_S2S(DV, true, false, true);                                             \
+    } else {                                                                              \
+      if (rb && km) LAUNCH_S2S(DV, false, true, true);                                    \
+      else if (rb) LAUNCH_S2S(DV, false, true, false);                                    \
+      else if (km) LAUNCH_S2S(DV, false, false, true);                                    \
+      else LAUNCH_S2S(DV, false, false, false);                                           \
+    }                                                                                     \
+  } while (0)
+  if (s2s.any) {
+    if (D == 64) LAUNCH_BWD_S2S(64); else LAUNCH_BWD_S2S(128);
+  } else
   switch (D) {
     case 64:
       if (sl != nullptr) LAUNCH_BWD(64, true); else LAUNCH_BWD(64, false);
@@ -409,6 +502,8 @@ std::vector<at::Tensor> flash_prefill_bwd(const at::Tensor& q, const at::Tensor&
       break;
     default: TORCH_CHECK(false, "flash_prefill_bwd: head dim must be 64, 96, 128 or 256");
   }
+#undef LAUNCH_BWD_S2S
+#undef LAUNCH_S2S
 #undef LAUNCH_BWD
   HIP_CHECK_LAST();
   return {dq, dk, dv};

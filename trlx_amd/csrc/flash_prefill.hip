@@ -22,6 +22,9 @@
 // to the scaled score fragments right after the QK^T MFMA, in fp32, so the
 // row max / logsumexp include the bias (common.h alibi_score).
 // GQA maps hq -> hkv = hq / (Hq/Hkv).  The backward is csrc/flash_backward.hip.
+// Seq2seq (T5) modes at head dims 64 / 128 — non-causal, Toeplitz relative-
+// position bias, arbitrary key mask, Tq != Tk — are template flags described
+// at the kernel; ops.seq2seq_attention is their entry point.
 //
 // Head dims: 64, 96, 128, 256.  D=96 (NeoX-20B) is the same plan (D/32 = 3
 // MFMA k-steps, D/8 = 12 vectors per row: every index below divides, none
@@ -54,7 +57,20 @@ typedef __attribute__((ext_vector_type(4))) float f32x4_fp;
 
 // ALIBI is a template parameter (not a runtime null test) so the no-bias
 // instantiation compiles to exactly the code it was before the bias existed.
-template <int D, bool ALIBI>
+// The seq2seq (T5) modes are template parameters for the same reason:
+//   CAUSAL off — the key loop runs over all Tk and `key <= qpos` leaves the
+//                validity test (encoder self-attention, cross-attention);
+//   RELB       — Toeplitz relative-position bias rel_bias[h, key - qpos +
+//                bias_zero] added to the fp32 score fragments right after the
+//                QK^T MFMA, before masking and the row max (common.h
+//                rel_bias_score); read through L1, a few KB per head;
+//   KMASK      — arbitrary uint8 key mask [B, Tk] (nonzero = visible) joins
+//                the validity predicate; a fully masked key tile leaves
+//                (m, l) = (-inf, 0) untouched for the next tile.
+// Their kernel arguments (rel_bias, bias_len, bias_zero, key_mask) are the
+// trailing pack S2S, empty for the causal instantiations (common.h s2s_view).
+template <int D, bool ALIBI, bool CAUSAL = true, bool RELB = false, bool KMASK = false,
+          typename... S2S>
 __global__ __launch_bounds__(FBLOCK, 2) void flash_prefill_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
     const int* __restrict__ key_starts,
@@ -62,7 +78,14 @@ __global__ __launch_bounds__(FBLOCK, 2) void flash_prefill_kernel(
     bf16_t* __restrict__ out,
     float* __restrict__ lse /* [B,Hq,T] logsumexp of the SCALED (+biased) scores; may be null */,
     int B, int Hq, int Hkv, int T, int Tk,
-    int Sk /* allocated token stride of k/v (cache prefill) */, int start_pos, float scale) {
+    int Sk /* allocated token stride of k/v (cache prefill) */, int start_pos, float scale,
+    S2S... s2s_args) {
+  static_assert(s2s_pack_ok(!CAUSAL || RELB || KMASK, sizeof...(S2S), 4),
+                "seq2seq arguments: (rel_bias, bias_len, bias_zero, key_mask) iff a mode is on");
+  const S2SView s2s = s2s_view(s2s_args...);
+  const float* __restrict__ rel_bias = s2s.rel_bias;          // read iff RELB
+  const unsigned char* __restrict__ key_mask = s2s.key_mask;  // read iff KMASK
+  const int bias_len = s2s.bias_len, bias_zero = s2s.bias_zero;
   constexpr int TK = fwd_tk(D);
   constexpr bool QREG = D > 128;  // Q as register-resident A-fragments, not LDS
   constexpr int DPAD = D + 8;    // LDS row stride (shorts), bank-staggered
@@ -136,7 +159,8 @@ __global__ __launch_bounds__(FBLOCK, 2) void flash_prefill_kernel(
   const bf16_t* vp = v + (((size_t)b * Hkv + hkv) * (size_t)Sk) * D;
 
   const int kt_lo = (kstart / TK) * TK;
-  const int kt_hi = min(Tk, qhi_pos + 1);  // no tile fully above the causal line
+  // causal: no tile fully above the causal line
+  const int kt_hi = CAUSAL ? min(Tk, qhi_pos + 1) : Tk;
 
   for (int kt = kt_lo; kt < kt_hi; kt += TK) {
     // ---- stage K tile + V tile (transposed) ---------------------------------
@@ -184,10 +208,20 @@ __global__ __launch_bounds__(FBLOCK, 2) void flash_prefill_kernel(
 #pragma unroll
         for (int r = 0; r < 4; ++r) sfrag[kk][r] = alibi_score(sfrag[kk][r], slope, key, kstart);
       }
+      if constexpr (RELB) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          sfrag[kk][r] = rel_bias_score(sfrag[kk][r], rel_bias + (size_t)h * bias_len, bias_len,
+                                        key, start_pos + q0 + qrow0 + (lane >> 4) * 4 + r,
+                                        bias_zero);
+      }
+      bool kvis = true;  // index clamped: lanes past Tk are masked by `key < Tk` anyway
+      if constexpr (KMASK) kvis = key_mask[(size_t)b * Tk + min(key, Tk - 1)] != 0;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int qrow = q0 + qrow0 + (lane >> 4) * 4 + r;
-        const bool valid = key < Tk && key >= kstart && key <= start_pos + qrow && qrow < T;
+        const bool valid = key < Tk && key >= kstart && (!CAUSAL || key <= start_pos + qrow) &&
+                           qrow < T && kvis;
         if (!valid) sfrag[kk][r] = -INFINITY;
       }
     }
@@ -281,13 +315,19 @@ std::vector<at::Tensor> flash_prefill_lse(const at::Tensor& q, const at::Tensor&
                                           const at::Tensor& v,
                                           const c10::optional<at::Tensor>& key_starts,
                                           long start_pos, double scale, long tk, bool want_lse,
-                                          const c10::optional<at::Tensor>& alibi_slopes);
+                                          const c10::optional<at::Tensor>& alibi_slopes,
+                                          const c10::optional<at::Tensor>& rel_bias,
+                                          long bias_zero,
+                                          const c10::optional<at::Tensor>& key_mask, bool causal);
 
 at::Tensor flash_prefill(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
                          const c10::optional<at::Tensor>& key_starts, long start_pos,
                          double scale, long tk,
-                         const c10::optional<at::Tensor>& alibi_slopes) {
-  return flash_prefill_lse(q, k, v, key_starts, start_pos, scale, tk, false, alibi_slopes)[0];
+                         const c10::optional<at::Tensor>& alibi_slopes,
+                         const c10::optional<at::Tensor>& rel_bias, long bias_zero,
+                         const c10::optional<at::Tensor>& key_mask, bool causal) {
+  return flash_prefill_lse(q, k, v, key_starts, start_pos, scale, tk, false, alibi_slopes,
+                           rel_bias, bias_zero, key_mask, causal)[0];
 }
 
 std::vector<at::Tensor> flash_prefill_lse(const at::Tensor& q, const at::Tensor& k,
@@ -295,7 +335,11 @@ std::vector<at::Tensor> flash_prefill_lse(const at::Tensor& q, const at::Tensor&
                                           const c10::optional<at::Tensor>& key_starts,
                                           long start_pos, double scale, long tk,
                                           bool want_lse,
-                                          const c10::optional<at::Tensor>& alibi_slopes) {
+                                          const c10::optional<at::Tensor>& alibi_slopes,
+                                          const c10::optional<at::Tensor>& rel_bias,
+                                          long bias_zero,
+                                          const c10::optional<at::Tensor>& key_mask,
+                                          bool causal) {
   TORCH_CHECK(q.is_cuda() && q.dtype() == at::kBFloat16 && q.dim() == 4 && q.is_contiguous());
   TORCH_CHECK(k.is_contiguous() && v.is_contiguous());
   const int B = q.size(0), Hq = q.size(1), T = q.size(2), D = q.size(3);
@@ -304,6 +348,9 @@ std::vector<at::Tensor> flash_prefill_lse(const at::Tensor& q, const at::Tensor&
   TORCH_CHECK(Tk <= Sk);
   TORCH_CHECK(k.size(3) == D && Hq % Hkv == 0);
   const float* sl = alibi_slopes_ptr(alibi_slopes, q, Hq, "flash_prefill");
+  const Seq2SeqArgs s2s =
+      seq2seq_args(rel_bias, bias_zero, key_mask, causal, key_starts.has_value(), sl != nullptr,
+                   q, B, Hq, T, Tk, start_pos, D, "flash_prefill");
   auto out = at::empty_like(q);
   auto lse = want_lse ? at::empty({B, Hq, T}, q.options().dtype(at::kFloat)) : at::Tensor();
   if (q.numel() == 0) return {out, lse};
@@ -324,6 +371,29 @@ std::vector<at::Tensor> flash_prefill_lse(const at::Tensor& q, const at::Tensor&
 #define LAUNCH_FWD(DV, AL)                                                              \
   flash_prefill_kernel<DV, AL><<<grid, FBLOCK, 0, stream>>>(                            \
       qp, kp, vp, ks, sl, op, lp, B, Hq, Hkv, T, Tk, Sk, (int)start_pos, (float)scale)
+#define LAUNCH_S2S(DV, CA, RB, KM)                                                       \
+  flash_prefill_kernel<DV, false, CA, RB, KM><<<grid, FBLOCK, 0, stream>>>(              \
+      qp, kp, vp, ks, sl, op, lp, B, Hq, Hkv, T, Tk, Sk, (int)start_pos, (float)scale,   \
+      s2s.rel_bias, s2s.bias_len, s2s.bias_zero, s2s.key_mask)
+  // seq2seq modes (head dims 64 / 128, checked in seq2seq_args): one
+  // instantiation per (causal, bias, mask) combination
+#define LAUNCH_FWD_S2S(DV)                                                               \
+  do {                                                                                   \
+    const bool rb = s2s.rel_bias != nullptr, km = s2s.key_mask != nullptr;               \
+    if (causal) {                                                                        \
+      if (rb && km) LAUNCH_S2S(DV, true, true, true);                                    \
+      else if (rb) LAUNCH_S2S(DV, true, true, false);                                    \
+      else LAUNCH_S2S(DV, true, false, true);                                            \
+    } else {                                                                             \
+      if (rb && km) LAUNCH_S2S(DV, false, true, true);                                   \
+      else if (rb) LAUNCH_S2S(DV, false, true, false);                                   \
+      else if (km) LAUNCH_S2S(DV, false, false, true);                                   \
+      else LAUNCH_S2S(DV, false, false, false);                                          \
+    }                                                                                    \
+  } while (0)
+  if (s2s.any) {
+    if (D == 64) LAUNCH_FWD_S2S(64); else LAUNCH_FWD_S2S(128);
+  } else
   switch (D) {
     case 64:
       if (sl != nullptr) LAUNCH_FWD(64, true); else LAUNCH_FWD(64, false);
@@ -340,6 +410,8 @@ std::vector<at::Tensor> flash_prefill_lse(const at::Tensor& q, const at::Tensor&
     default:
       TORCH_CHECK(false, "flash_prefill: head dim must be 64, 96, 128 or 256, got ", D);
   }
+#undef LAUNCH_FWD_S2S
+#undef LAUNCH_S2S
 #undef LAUNCH_FWD
   HIP_CHECK_LAST();
   return {out, lse};

@@ -25,6 +25,7 @@ from .nn.seq2seq import (
     seq2seq_config_to_hf,
     seq2seq_state_dict_from_hf,
     seq2seq_state_dict_to_hf,
+    run_decoder_blocks,
 )
 
 logger = logging.get_logger(__name__)
@@ -124,18 +125,8 @@ class T5ValueBranch(nn.Module):
 
     def forward(self, hidden, enc_out, attention_mask, decoder_attention_mask,
                 position_bias, logits_slice=None):
-        from .nn.seq2seq import _extend_mask
-
-        B, T = hidden.shape[:2]
-        causal = torch.ones(T, T, device=hidden.device).tril()
-        self_mask = (1.0 - causal[None, None]) * torch.finfo(torch.float32).min
-        if decoder_attention_mask is not None:
-            self_mask = self_mask + _extend_mask(decoder_attention_mask)
-        cross_mask = _extend_mask(attention_mask)
-        h = hidden
-        for block in self.blocks:
-            h, position_bias, _, _ = block(h, enc_out=enc_out, self_mask=self_mask,
-                                           cross_mask=cross_mask, position_bias=position_bias)
+        h = run_decoder_blocks(self.blocks, hidden, enc_out, attention_mask,
+                               decoder_attention_mask, position_bias)
         h = self.final_norm(h)
         if logits_slice is not None:
             h = h[:, logits_slice[0] : logits_slice[1]]
@@ -156,7 +147,7 @@ class AutoModelForSeq2SeqLMWithValueHead(Seq2SeqModelWrapper):
             self.v_branch = T5ValueBranch(base_model, num_value_layers_unfrozen)
 
     def _value_bias(self, T, device):
-        return self.base_model.decoder_blocks[0].self_attn.compute_bias(T, T, device)
+        return self.base_model.decoder_bias(T, device)
 
     def forward(self, input_ids, attention_mask=None, decoder_input_ids=None,
                 decoder_attention_mask=None, return_ref_logits: bool = False,
@@ -201,19 +192,9 @@ class T5Branch(nn.Module):
 
     def forward(self, hidden, enc_out, attention_mask, decoder_attention_mask,
                 position_bias, logits_slice=None):
-        from .nn.seq2seq import _extend_mask
-
         with torch.no_grad():
-            B, T = hidden.shape[:2]
-            causal = torch.ones(T, T, device=hidden.device).tril()
-            self_mask = (1.0 - causal[None, None]) * torch.finfo(torch.float32).min
-            if decoder_attention_mask is not None:
-                self_mask = self_mask + _extend_mask(decoder_attention_mask)
-            cross_mask = _extend_mask(attention_mask)
-            h = hidden
-            for block in self.blocks:
-                h, position_bias, _, _ = block(h, enc_out=enc_out, self_mask=self_mask,
-                                               cross_mask=cross_mask, position_bias=position_bias)
+            h = run_decoder_blocks(self.blocks, hidden, enc_out, attention_mask,
+                                   decoder_attention_mask, position_bias)
             h = self.final_norm(h)
             if logits_slice is not None:
                 h = h[:, logits_slice[0] : logits_slice[1]]
@@ -258,9 +239,8 @@ class AutoModelForSeq2SeqLMWithHydraValueHead(AutoModelForSeq2SeqLMWithValueHead
             values = self.v_head(ds.to(self.v_head[0].weight.dtype)).squeeze(-1).float()
         ref_logits = None
         if return_ref_logits and self.frozen_head is not None:
-            # recompute the first unfrozen block's incoming position bias
-            bias_layer = self.base_model.decoder_blocks[0].self_attn
-            position_bias = bias_layer.compute_bias(T, T, dec.device)
+            # the first unfrozen block's incoming position bias
+            position_bias = self.base_model.decoder_bias(T, dec.device)
             ref_hidden = hidden_at[-self.num_layers_unfrozen] if isinstance(hidden_at, dict) \
                 else hidden_at
             ref_logits = self.frozen_head(ref_hidden, enc, attention_mask,

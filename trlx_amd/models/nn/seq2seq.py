@@ -6,13 +6,24 @@ kernel), relative-position-bucket attention bias held by layer 0 of each
 stack, UNSCALED q@k^T scores, relu or gated-gelu FFN, and the d_model^-0.5
 output rescale under tied embeddings.
 
-Attention here runs eager (rocBLAS GEMMs + additive-bias softmax) because the
-T5 bias breaks the causal-softmax kernel's mask-free contract; norms, logprob
-gathers and sampling still hit the gfx950 kernels.  Decoder generation keeps a
-KV cache and precomputes cross-attention K/V once per prompt.
+Attention: full-sequence passes (encoder, teacher-forced decoder, cross-
+attention, the hydra and value branches) can run in the gfx950 flash kernels'
+seq2seq modes (``ops.seq2seq_attention``: non-causal, Toeplitz relative-
+position bias, arbitrary key mask, Tq != Tk) — bf16 on the GPU, head dim 64 or
+128, and ``ops.seq2seq_flash_enabled`` (on by default at both head dims, see
+profiles/t5_attention_notes.md; ``TRLX_AMD_NO_FLASH_PREFILL`` /
+``TRLX_AMD_NO_FLASH_TRAIN`` = 1 turn it off).  The kernels produce no gradient for the
+learned bias, so a layer whose bias table requires grad keeps the eager path
+(rocBLAS GEMMs + additive-bias softmax) under grad mode: with
+``num_layers_unfrozen > 0`` the tables are frozen and every attention
+qualifies; a fully unfrozen T5 trains its self-attention eager (its cross-
+attention and its no_grad passes still qualify).  The per-token generation
+step (``past_kv``) stays eager, and so does everything on CPU.  Dropout is
+not applied to attention probabilities on either path.  Norms, logprob
+gathers and sampling hit the gfx950 kernels.  Decoder generation keeps a KV
+cache and precomputes cross-attention K/V once per prompt.
 """
 
-import math
 from dataclasses import dataclass, field
 from typing import Any, Dict, Optional, Tuple
 
@@ -21,6 +32,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ... import ops
+from ...ops.reference import relative_position_bucket  # noqa: F401  (re-exported)
 
 
 @dataclass
@@ -60,27 +72,6 @@ class Seq2SeqConfig:
         return cls(**d)
 
 
-def relative_position_bucket(relative_position: torch.Tensor, bidirectional: bool,
-                             num_buckets: int, max_distance: int) -> torch.Tensor:
-    """T5's log-bucketed relative positions (semantics of the T5 paper)."""
-    ret = torch.zeros_like(relative_position)
-    n = -relative_position
-    if bidirectional:
-        num_buckets //= 2
-        ret = ret + (n < 0).long() * num_buckets
-        n = n.abs()
-    else:
-        n = torch.clamp(n, min=0)
-    max_exact = num_buckets // 2
-    is_small = n < max_exact
-    val_large = max_exact + (
-        torch.log(n.float() / max_exact + 1e-9) / math.log(max_distance / max_exact)
-        * (num_buckets - max_exact)
-    ).long()
-    val_large = torch.clamp(val_large, max=num_buckets - 1)
-    return ret + torch.where(is_small, n, val_large)
-
-
 class T5Norm(nn.Module):
     """T5LayerNorm == RMSNorm (the fused HIP kernel path)."""
 
@@ -91,6 +82,127 @@ class T5Norm(nn.Module):
 
     def forward(self, x):
         return ops.rmsnorm(x, self.weight, self.eps)
+
+
+def _extend_mask(mask: Optional[torch.Tensor], dtype=torch.float32) -> Optional[torch.Tensor]:
+    """[B, T] 1/0 -> additive [B, 1, 1, T]."""
+    if mask is None:
+        return None
+    return (1.0 - mask[:, None, None, :].float()) * torch.finfo(dtype).min
+
+
+class RelBias:
+    """The position bias of one pass over a stack, in both forms, each built
+    lazily where its path runs: ``dense()`` is ``owner.compute_bias`` ([1, H,
+    Tq, Tk], the eager path's additive bias) and ``vec()`` the Toeplitz vector
+    ``(rel_bias [H, L] fp32, bias_zero)`` the kernels read.  ``owner`` is the
+    attention layer that holds the table."""
+
+    def __init__(self, owner: "T5Attention", q_len: int, k_len: int, device, q_offset: int = 0):
+        self.owner, self.q_len, self.k_len, self.q_offset = owner, q_len, k_len, q_offset
+        self.device = device
+        self._dense = None
+        self._vec = None
+
+    @property
+    def table(self) -> torch.Tensor:
+        return self.owner.relative_attention_bias.weight
+
+    def dense(self) -> torch.Tensor:
+        if self._dense is None:
+            self._dense = self.owner.compute_bias(self.q_len, self.k_len, self.device,
+                                                  q_offset=self.q_offset)
+        return self._dense
+
+    def vec(self) -> Tuple[torch.Tensor, int]:
+        if self._vec is None:
+            cfg = self.owner.cfg
+            self._vec = ops.t5_rel_bias(
+                self.table, self.q_len, self.k_len, self.q_offset, self.owner.bidirectional,
+                cfg.relative_attention_num_buckets, cfg.relative_attention_max_distance)
+        return self._vec
+
+
+class AttnMask:
+    """What one attention call may see, in both forms: the raw ``key_mask``
+    [B, Tk] (1 = visible, or None) plus the ``causal`` flag for the kernels,
+    and ``additive()``, the [B, 1, Tq, Tk] float mask the eager path adds to
+    the scores — built on first use only (like make_context's ALiBi bias)."""
+
+    def __init__(self, key_mask: Optional[torch.Tensor], causal: bool = False, q_len: int = 0,
+                 past_len: int = 0, device=None):
+        self.key_mask, self.causal = key_mask, causal
+        self.q_len, self.past_len, self.device = q_len, past_len, device
+        self._additive = None
+        self._built = False
+        self._uint8 = None
+
+    def uint8(self) -> Optional[torch.Tensor]:
+        """``key_mask`` as the contiguous uint8 [B, Tk] the kernels read,
+        converted once per pass, not once per attention call."""
+        if self._uint8 is None and self.key_mask is not None:
+            km = self.key_mask
+            if km.dtype != torch.uint8:
+                km = (km != 0).to(torch.uint8)
+            self._uint8 = km.contiguous()
+        return self._uint8
+
+    def additive(self) -> Optional[torch.Tensor]:
+        if not self._built:
+            self._built = True
+            mask = None
+            if self.causal:  # causal mask over [T, past+T]
+                total = self.past_len + self.q_len
+                causal = torch.ones(self.q_len, total, device=self.device).tril(
+                    diagonal=self.past_len)
+                mask = (1.0 - causal[None, None]) * torch.finfo(torch.float32).min
+                if self.key_mask is not None:
+                    mask = mask + _extend_mask(self.key_mask)
+            else:
+                mask = _extend_mask(self.key_mask)
+            self._additive = mask
+        return self._additive
+
+
+@dataclass
+class AttnContext:
+    """Masks of one pass over a stack: ``self_attn`` for the stack's own
+    tokens, ``cross`` for the encoder keys (decoder stacks only)."""
+    self_attn: AttnMask
+    cross: Optional[AttnMask] = None
+
+
+def encoder_context(attention_mask: Optional[torch.Tensor]) -> AttnContext:
+    return AttnContext(AttnMask(attention_mask))
+
+
+def decoder_context(q_len: int, device, attention_mask: Optional[torch.Tensor] = None,
+                    decoder_attention_mask: Optional[torch.Tensor] = None,
+                    past_len: int = 0) -> AttnContext:
+    """The one place decoder-side masks are built: ``Seq2SeqTransformer.decode``,
+    the hydra branch and the value branch all pass over decoder blocks with a
+    causal self-attention mask (+ optional decoder padding) and the encoder's
+    padding mask on the cross-attention."""
+    return AttnContext(
+        AttnMask(decoder_attention_mask, causal=True, q_len=q_len, past_len=past_len,
+                 device=device),
+        AttnMask(attention_mask))
+
+
+def run_decoder_blocks(blocks, hidden, enc_out, attention_mask=None,
+                       decoder_attention_mask=None, position_bias=None):
+    """Full-sequence pass of ``hidden`` through decoder ``blocks`` (the model's
+    own top layers or a branch's copies of them) with the decoder-side masks."""
+    ctx = decoder_context(hidden.shape[1], hidden.device, attention_mask,
+                          decoder_attention_mask)
+    h = hidden
+    for block in blocks:
+        h, position_bias, _, _ = block(h, enc_out=enc_out, position_bias=position_bias, ctx=ctx)
+    return h
+
+
+def _on_gpu_bf16(t: torch.Tensor) -> bool:
+    return t.is_cuda and t.dtype == torch.bfloat16
 
 
 class T5Attention(nn.Module):
@@ -124,9 +236,31 @@ class T5Attention(nn.Module):
     def _shape(self, x, B, T):
         return x.view(B, T, self.num_heads, self.d_kv).transpose(1, 2)
 
-    def forward(self, x, kv_input=None, mask=None, position_bias=None, past_kv=None):
-        """``mask``: additive float mask [B, 1, Tq, Tk] (0 / -inf).  Returns
-        (out, position_bias, new_kv)."""
+    def _takes_kernel(self, q, k, v, mask, position_bias, past_kv, attn_mask) -> bool:
+        """Does this call run in ``ops.seq2seq_attention``?  A full-sequence
+        pass on the GPU in bf16 whose masks came as an ``AttnMask`` and whose
+        bias (if any) as a ``RelBias`` with a table that gets no gradient."""
+        if attn_mask is None or mask is not None or past_kv is not None:
+            return False
+        if not (_on_gpu_bf16(q) and _on_gpu_bf16(k) and _on_gpu_bf16(v)):
+            return False
+        grad = torch.is_grad_enabled()
+        if position_bias is not None:
+            if not isinstance(position_bias, RelBias):
+                return False
+            if grad and position_bias.table.requires_grad:
+                return False  # the kernels produce no gradient for the learned bias
+        train = grad and (q.requires_grad or k.requires_grad or v.requires_grad)
+        return ops.seq2seq_flash_enabled(self.d_kv, train)
+
+    def forward(self, x, kv_input=None, mask=None, position_bias=None, past_kv=None,
+                attn_mask: Optional[AttnMask] = None):
+        """``mask``: additive float mask [B, 1, Tq, Tk] (0 / -inf), or
+        ``attn_mask``: the same visibility as an ``AttnMask`` (raw key mask +
+        causal flag; the additive form is built only if the eager path runs).
+        ``position_bias``: a dense [1, H, Tq, Tk] tensor or a ``RelBias``; with
+        ``attn_mask`` a layer that owns a table creates a ``RelBias``.
+        Returns (out, position_bias, new_kv)."""
         B, Tq, _ = x.shape
         q = self._shape(self.q(x), B, Tq)
         if kv_input is None:  # self-attention
@@ -145,13 +279,27 @@ class T5Attention(nn.Module):
             v = self._shape(self.v(kv_input), B, Tk)
             new_kv = (k, v)
 
-        # T5: NO 1/sqrt(d) scaling
-        scores = torch.matmul(q, k.transpose(-1, -2)).float()
         if position_bias is None and self.relative_attention_bias is not None:
             q_offset = k.shape[2] - Tq
-            position_bias = self.compute_bias(Tq, k.shape[2], x.device, q_offset=q_offset)
-        if position_bias is not None:
-            scores = scores + position_bias.float()
+            if attn_mask is not None:
+                position_bias = RelBias(self, Tq, k.shape[2], x.device, q_offset=q_offset)
+            else:
+                position_bias = self.compute_bias(Tq, k.shape[2], x.device, q_offset=q_offset)
+
+        # T5: NO 1/sqrt(d) scaling
+        if self._takes_kernel(q, k, v, mask, position_bias, past_kv, attn_mask):
+            vec, zero = position_bias.vec() if position_bias is not None else (None, 0)
+            out = ops.seq2seq_attention(q, k, v, rel_bias=vec, bias_zero=zero,
+                                        key_mask=attn_mask.uint8(), causal=attn_mask.causal,
+                                        start_pos=0, scale=1.0)
+            return self.o(out.transpose(1, 2).reshape(B, Tq, -1)), position_bias, new_kv
+
+        scores = torch.matmul(q, k.transpose(-1, -2)).float()
+        if mask is None and attn_mask is not None:
+            mask = attn_mask.additive()
+        dense = position_bias.dense() if isinstance(position_bias, RelBias) else position_bias
+        if dense is not None:
+            scores = scores + dense.float()
         if mask is not None:
             scores = scores + mask.float()
         probs = torch.softmax(scores, dim=-1).to(v.dtype)
@@ -191,15 +339,20 @@ class T5Block(nn.Module):
         self.ffn = T5FFN(cfg)
 
     def forward(self, x, enc_out=None, self_mask=None, cross_mask=None, position_bias=None,
-                cross_bias=None, past_self_kv=None, past_cross_kv=None):
+                cross_bias=None, past_self_kv=None, past_cross_kv=None,
+                ctx: Optional[AttnContext] = None):
+        """Masks come either as additive tensors (``self_mask`` / ``cross_mask``)
+        or as one ``AttnContext`` (``ctx``) that serves both attention paths."""
         h, position_bias, new_self_kv = self.self_attn(
-            self.self_norm(x), mask=self_mask, position_bias=position_bias, past_kv=past_self_kv)
+            self.self_norm(x), mask=self_mask, position_bias=position_bias, past_kv=past_self_kv,
+            attn_mask=ctx.self_attn if ctx is not None and self_mask is None else None)
         x = x + h
         new_cross_kv = None
         if self.is_decoder and enc_out is not None:
             h, _, new_cross_kv = self.cross_attn(
                 self.cross_norm(x), kv_input=enc_out, mask=cross_mask, position_bias=cross_bias,
-                past_kv=past_cross_kv)
+                past_kv=past_cross_kv,
+                attn_mask=ctx.cross if ctx is not None and cross_mask is None else None)
             x = x + h
         x = x + self.ffn(self.ffn_norm(x))
         return x, position_bias, new_self_kv, new_cross_kv
@@ -211,13 +364,6 @@ class Seq2SeqOutput:
     last_hidden_state: Optional[torch.Tensor] = None
     encoder_last_hidden_state: Optional[torch.Tensor] = None
     decoder_hidden_at_layer: Optional[torch.Tensor] = None
-
-
-def _extend_mask(mask: Optional[torch.Tensor], dtype=torch.float32) -> Optional[torch.Tensor]:
-    """[B, T] 1/0 -> additive [B, 1, 1, T]."""
-    if mask is None:
-        return None
-    return (1.0 - mask[:, None, None, :].float()) * torch.finfo(dtype).min
 
 
 class Seq2SeqTransformer(nn.Module):
@@ -251,10 +397,10 @@ class Seq2SeqTransformer(nn.Module):
 
     def encode(self, input_ids, attention_mask=None):
         h = self.shared(input_ids)
-        mask = _extend_mask(attention_mask)
+        ctx = encoder_context(attention_mask)
         bias = None
         for block in self.encoder_blocks:
-            h, bias, _, _ = block(h, self_mask=mask, position_bias=bias)
+            h, bias, _, _ = block(h, position_bias=bias, ctx=ctx)
         return self.encoder_final_norm(h)
 
     # --- decoder ------------------------------------------------------------
@@ -266,13 +412,8 @@ class Seq2SeqTransformer(nn.Module):
         B, T = decoder_input_ids.shape
         h = self.shared(decoder_input_ids)
         past_len = past[0][0][0].shape[2] if past is not None and past[0][0] is not None else 0
-        # causal mask over [T, past+T]
-        total = past_len + T
-        causal = torch.ones(T, total, device=h.device).tril(diagonal=past_len)
-        self_mask = (1.0 - causal[None, None]) * torch.finfo(torch.float32).min
-        if decoder_attention_mask is not None:
-            self_mask = self_mask + _extend_mask(decoder_attention_mask)
-        cross_mask = _extend_mask(attention_mask)
+        ctx = decoder_context(T, h.device, attention_mask, decoder_attention_mask,
+                              past_len=past_len)
 
         bias = None
         new_past = []
@@ -295,10 +436,16 @@ class Seq2SeqTransformer(nn.Module):
             p_self = past[i][0] if past is not None else None
             p_cross = past[i][1] if past is not None else None
             h, bias, self_kv, cross_kv = block(
-                h, enc_out=enc_out, self_mask=self_mask, cross_mask=cross_mask,
-                position_bias=bias, past_self_kv=p_self, past_cross_kv=p_cross)
+                h, enc_out=enc_out, position_bias=bias, past_self_kv=p_self,
+                past_cross_kv=p_cross, ctx=ctx)
             new_past.append((self_kv, cross_kv))
         return self.decoder_final_norm(h), new_past, hidden_at
+
+    def decoder_bias(self, q_len: int, device) -> RelBias:
+        """The decoder's self-attention position bias for a full pass over
+        ``q_len`` tokens, as the hydra and value branches need it to re-enter
+        the stack above block 0 (which owns the table)."""
+        return RelBias(self.decoder_blocks[0].self_attn, q_len, q_len, device)
 
     def project(self, hidden):
         if self.config.tie_word_embeddings:

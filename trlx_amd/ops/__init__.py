@@ -54,6 +54,36 @@ def flash_enabled(head_dim: int, train: bool) -> bool:
         return False
     return switch == "0" or head_dim in FLASH_TRAIN_DEFAULT_DIMS
 
+
+# The seq2seq (T5) modes of the same kernels — non-causal, Toeplitz relative
+# bias, arbitrary key mask, Tq != Tk — exist at these head dims only (t5-small
+# through 11b and flan-t5).  Their defaults follow the same rule, measured by
+# tools/bench_t5_attention.py against the eager matmul -> softmax -> matmul
+# sequence and recorded in profiles/t5_attention_notes.md: every (head dim,
+# direction) pair measured faster than eager (D=128 forward+backward by 3%,
+# everything else by 2x or more), so all four are defaults.
+SEQ2SEQ_FLASH_HEAD_DIMS = (64, 128)
+SEQ2SEQ_FLASH_PREFILL_DEFAULT_DIMS = (64, 128)
+SEQ2SEQ_FLASH_TRAIN_DEFAULT_DIMS = (64, 128)
+
+
+def seq2seq_flash_enabled(head_dim: int, train: bool) -> bool:
+    """``flash_enabled`` for the T5 attention path (``ops.seq2seq_attention``):
+    the same two switches with the same meaning (``1`` off, ``0`` on, unset
+    follows the measured defaults), over the seq2seq default sets."""
+    if head_dim not in SEQ2SEQ_FLASH_HEAD_DIMS:
+        return False
+    prefill = os.environ.get("TRLX_AMD_NO_FLASH_PREFILL")
+    if prefill == "1":
+        return False
+    if not train:
+        return prefill == "0" or head_dim in SEQ2SEQ_FLASH_PREFILL_DEFAULT_DIMS
+    switch = os.environ.get("TRLX_AMD_NO_FLASH_TRAIN")
+    if switch == "1":
+        return False
+    return switch == "0" or head_dim in SEQ2SEQ_FLASH_TRAIN_DEFAULT_DIMS
+
+
 _EXT = None
 _EXT_TRIED = False
 _EXT_ERR: Optional[str] = None
@@ -888,3 +918,89 @@ def flash_attention(q, k, v, key_starts=None, scale: float = 1.0, alibi_slopes=N
     ks = key_starts.to(torch.int32).contiguous() if key_starts is not None else None
     return _FlashAttention.apply(q.contiguous(), k.contiguous(), v.contiguous(), ks,
                                  float(scale), ext, alibi_slopes)
+
+
+# --------------------------------------------------------------------------
+# seq2seq (T5) attention: relative-position bias, key masks, cross-attention
+# --------------------------------------------------------------------------
+
+
+def t5_rel_bias(table: torch.Tensor, q_len: int, k_len: int, q_offset: int = 0,
+                bidirectional: bool = True, num_buckets: int = 32,
+                max_distance: int = 128) -> Tuple[torch.Tensor, int]:
+    """The T5 relative-position bias in the form the kernels read: a per-head
+    Toeplitz vector ``rel_bias`` [H, L] fp32 and ``bias_zero``, the index of
+    relative position 0 (``reference.t5_rel_bias`` has the layout).  Plain
+    torch on every device — one embedding lookup of L rows — and differentiable
+    with respect to ``table`` (the [num_buckets, H] embedding weight)."""
+    return reference.t5_rel_bias(table, q_len, k_len, q_offset, bidirectional, num_buckets,
+                                 max_distance)
+
+
+class _Seq2SeqAttention(torch.autograd.Function):
+    """Differentiable seq2seq flash attention: like ``_FlashAttention`` it saves
+    (q, k, v, out, lse) and recomputes P in the backward kernels.  ``rel_bias``
+    and ``key_mask`` are constants here (the kernels produce no bias gradient)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, rel_bias, bias_zero, key_mask, causal, start_pos, scale, ext):
+        out, lse = ext.flash_prefill_lse(q, k, v, None, start_pos, scale, 0, True, None,
+                                         rel_bias, bias_zero, key_mask, causal)
+        ctx.save_for_backward(q, k, v, out, lse)
+        ctx.rel_bias, ctx.key_mask, ctx.causal = rel_bias, key_mask, causal
+        # the backward kernels have no start_pos: the bias index is
+        # key - (start_pos + row) + bias_zero, so the offset folds into bias_zero
+        ctx.bias_zero = bias_zero - start_pos
+        ctx.scale = scale
+        ctx.ext = ext
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, out, lse = ctx.saved_tensors
+        dq, dk, dv = ctx.ext.flash_prefill_bwd(q, k, v, out, dout, lse, None, ctx.scale, None,
+                                               ctx.rel_bias, ctx.bias_zero, ctx.key_mask,
+                                               ctx.causal)
+        return dq, dk, dv, None, None, None, None, None, None, None
+
+
+def seq2seq_attention(q, k, v, rel_bias=None, bias_zero: int = 0, key_mask=None,
+                      causal: bool = False, start_pos: int = 0, scale: float = 1.0):
+    """Flash attention for encoder-decoder models (csrc/flash_prefill.hip and
+    flash_backward.hip in their seq2seq modes): q [B,Hq,Tq,D] bf16, k/v
+    [B,Hkv,Tk,D], ``Tq != Tk`` allowed when not ``causal`` (cross-attention).
+
+    ``rel_bias`` [Hq, L] fp32 with ``bias_zero`` is the Toeplitz T5 bias of
+    ``t5_rel_bias``; ``key_mask`` [B, Tk] is any visibility mask (nonzero =
+    visible, no contiguity assumed, no host sync; a contiguous uint8 mask is
+    used as it is, anything else is converted here on every call); a query row
+    with no visible key returns zeros.  K and V rows at masked keys must be
+    finite (they enter the backward as ``0 * x``).  Under ``no_grad``, or when no input requires grad, the
+    forward-only kernel runs; otherwise the forward saves the row logsumexp
+    and the backward kernels produce dq/dk/dv.  ``rel_bias`` gets NO gradient
+    from the kernels, so a bias that requires grad is an error under grad mode
+    (models keep a trainable table on the eager path).  On CPU the fp32
+    reference runs."""
+    if rel_bias is not None and rel_bias.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError(
+            "seq2seq_attention: rel_bias requires grad, but the kernels produce no bias "
+            "gradient; detach it or keep this attention on the eager path")
+    ext = _require_ext("seq2seq_attention")
+    if ext is None or not q.is_cuda:
+        return reference.seq2seq_attention(q, k, v, rel_bias, bias_zero, key_mask, causal,
+                                           start_pos, scale).to(q.dtype)
+    km = None
+    if key_mask is not None:
+        km = key_mask if key_mask.dtype == torch.uint8 else (key_mask != 0).to(torch.uint8)
+        km = km.contiguous()
+    rb = rel_bias.detach() if rel_bias is not None else None
+    q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+    needs_grad = torch.is_grad_enabled() and (q.requires_grad or k.requires_grad
+                                              or v.requires_grad)
+    if not needs_grad:
+        return ext.flash_prefill(q, k, v, None, int(start_pos), float(scale), 0, None, rb,
+                                 int(bias_zero), km, bool(causal))
+    if causal and (start_pos != 0 or q.shape[2] != k.shape[2]):
+        raise RuntimeError("seq2seq_attention: causal training needs Tq == Tk and start_pos == 0")
+    return _Seq2SeqAttention.apply(q, k, v, rb, int(bias_zero), km, bool(causal),
+                                   int(start_pos), float(scale), ext)

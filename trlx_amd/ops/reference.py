@@ -7,6 +7,7 @@ refuses to fall back here unless explicitly allowed — the HIP path must be
 the one that runs.
 """
 
+import math
 from typing import Optional, Tuple
 
 import torch
@@ -253,4 +254,89 @@ def flash_prefill(q, k, v, key_starts=None, start_pos: int = 0, scale: float = 1
     scores = scores.masked_fill(~mask, float("-inf"))
     probs = torch.softmax(scores, dim=-1)
     probs = torch.nan_to_num(probs, nan=0.0)
+    return torch.matmul(probs, vv).to(q.dtype)
+
+
+# --------------------------------------------------------------------------
+# T5 / seq2seq attention: Toeplitz relative-position bias + arbitrary key mask
+# --------------------------------------------------------------------------
+
+
+def relative_position_bucket(relative_position: torch.Tensor, bidirectional: bool,
+                             num_buckets: int, max_distance: int) -> torch.Tensor:
+    """T5's log-bucketed relative positions (semantics of the T5 paper)."""
+    ret = torch.zeros_like(relative_position)
+    n = -relative_position
+    if bidirectional:
+        num_buckets //= 2
+        ret = ret + (n < 0).long() * num_buckets
+        n = n.abs()
+    else:
+        n = torch.clamp(n, min=0)
+    max_exact = num_buckets // 2
+    is_small = n < max_exact
+    val_large = max_exact + (
+        torch.log(n.float() / max_exact + 1e-9) / math.log(max_distance / max_exact)
+        * (num_buckets - max_exact)
+    ).long()
+    val_large = torch.clamp(val_large, max=num_buckets - 1)
+    return ret + torch.where(is_small, n, val_large)
+
+
+def t5_rel_bias(table: torch.Tensor, q_len: int, k_len: int, q_offset: int = 0,
+                bidirectional: bool = True, num_buckets: int = 32,
+                max_distance: int = 128) -> Tuple[torch.Tensor, int]:
+    """The T5 position bias as a per-head Toeplitz vector.
+
+    The bias of (query position ``q_offset + i``, key ``j``) depends only on
+    ``j - (q_offset + i)``, so ``[H, Tq, Tk]`` collapses to ``[H, L]`` with
+    ``L = q_offset + q_len - 1 + k_len`` and relative position 0 at index
+    ``bias_zero = q_offset + q_len - 1``:
+    ``dense[h, i, j] == vec[h, j - (q_offset + i) + bias_zero]``.
+    ``table``: the ``[num_buckets, H]`` embedding weight; the lookup is an
+    embedding, so the result is differentiable with respect to it.
+    Returns ``(vec [H, L] fp32 contiguous, bias_zero)``."""
+    zero = q_offset + q_len - 1
+    L = zero + k_len
+    rel = torch.arange(L, device=table.device) - zero
+    buckets = relative_position_bucket(rel, bidirectional, num_buckets, max_distance)
+    vec = torch.nn.functional.embedding(buckets, table)  # [L, H]
+    return vec.t().float().contiguous(), zero
+
+
+def gather_rel_bias(rel_bias: torch.Tensor, bias_zero: int, q_len: int, k_len: int,
+                    start_pos: int = 0) -> torch.Tensor:
+    """Dense [H, Tq, Tk] bias from the Toeplitz vector of ``t5_rel_bias``
+    (query row i stands at position ``start_pos + i``)."""
+    qpos = torch.arange(q_len, device=rel_bias.device)[:, None] + start_pos
+    key = torch.arange(k_len, device=rel_bias.device)[None, :]
+    return rel_bias[:, key - qpos + bias_zero]
+
+
+def seq2seq_attention(q, k, v, rel_bias=None, bias_zero: int = 0, key_mask=None,
+                      causal: bool = False, start_pos: int = 0, scale: float = 1.0):
+    """fp32 reference for the seq2seq (T5) modes of the flash kernels: q
+    [B,Hq,Tq,D], k/v [B,Hkv,Tk,D] with Tq != Tk allowed.  The score of (query
+    row i, key j) is ``scale * q.k + rel_bias[h, j - (start_pos + i) +
+    bias_zero]``; key j is visible iff ``key_mask[b, j] != 0`` (any mask, not
+    only padding) and, under ``causal``, ``j <= start_pos + i``.  A row with no
+    visible key returns zeros."""
+    B, Hq, Tq, D = q.shape
+    Hkv, Tk = k.shape[1], k.shape[2]
+    kk, vv = k.float(), v.float()
+    if Hq != Hkv:
+        kk = kk.repeat_interleave(Hq // Hkv, dim=1)
+        vv = vv.repeat_interleave(Hq // Hkv, dim=1)
+    scores = torch.matmul(q.float() * scale, kk.transpose(-1, -2))
+    if rel_bias is not None:
+        scores = scores + gather_rel_bias(rel_bias.float(), bias_zero, Tq, Tk, start_pos)[None]
+    visible = torch.ones(B, 1, Tq, Tk, dtype=torch.bool, device=q.device)
+    if key_mask is not None:
+        visible = visible & (key_mask.to(q.device) != 0).view(B, 1, 1, Tk)
+    if causal:
+        i = torch.arange(Tq, device=q.device).view(1, 1, Tq, 1)
+        j = torch.arange(Tk, device=q.device).view(1, 1, 1, Tk)
+        visible = visible & (j <= start_pos + i)
+    scores = scores.masked_fill(~visible, float("-inf"))
+    probs = torch.nan_to_num(torch.softmax(scores, dim=-1), nan=0.0)
     return torch.matmul(probs, vv).to(q.dtype)
