@@ -98,6 +98,25 @@ def test_flash_backward_padded_rows_zero_grad():
     assert k.grad[1].abs().sum() > 0
 
 
+def test_flash_backward_checks_key_starts():
+    """The backward binding validates key_starts before any launch: int32, one
+    element per batch row (the kernels index it by batch row)."""
+    torch.manual_seed(4)
+    B, H, T, D = 2, 2, 16, 64
+    dev = "cuda"
+    q, k, v, dout = ((torch.randn(B, H, T, D, device=dev) * 0.5).bfloat16() for _ in range(4))
+    ks = torch.tensor([3, 0], device=dev, dtype=torch.int32)
+    out, lse = EXT.flash_prefill_lse(q, k, v, ks, 0, 0.125, 0, True)
+    with pytest.raises(RuntimeError, match="key_starts"):
+        EXT.flash_prefill_bwd(q, k, v, out, dout, lse, ks.long(), 0.125)
+    with pytest.raises(RuntimeError, match="key_starts"):
+        EXT.flash_prefill_bwd(q, k, v, out, dout, lse,
+                              torch.zeros(B + 1, device=dev, dtype=torch.int32), 0.125)
+    dq, dk, dv = EXT.flash_prefill_bwd(q, k, v, out, dout, lse, ks, 0.125)
+    assert dq.shape == q.shape and dk.shape == k.shape and dv.shape == v.shape
+    assert torch.isfinite(dq.float()).all() and torch.all(dk[0, :, :3] == 0)
+
+
 def test_model_training_grads_flash_vs_materializing():
     """One CE training step: parameter grads with the flash training path must
     match the materializing-softmax path."""

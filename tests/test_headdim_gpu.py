@@ -283,6 +283,106 @@ def test_fused_decode_attention_d96_rope():
 
 
 # --------------------------------------------------------------------------
+# decode instantiations no other op-level test launches
+# --------------------------------------------------------------------------
+# attention_decode: (D, ALiBi) is 5 x 2; test_ops.py has D=64/128 without the
+# bias, test_alibi_gpu.py D=32/64/128/256 with it, this file D=96 both ways.
+# fused_decode_attention: (D, mode) is 5 x 3; test_alibi_gpu.py has ALiBi at
+# D=64/128 and this file non-interleaved RoPE at D=96.  The cases below are the
+# rest.  Inputs come from the CPU generator, so the references (and the checks
+# that a wrong mode would move them) do not depend on the device.
+
+
+def _cpu_rand(*shape):
+    return (torch.randn(*shape) * 0.5).bfloat16()
+
+
+@pytest.mark.parametrize("D", [32, 256])
+def test_attention_decode_plain_d32_d256(D):
+    torch.manual_seed(8)
+    B, Hq, Hkv, S = 2, 4, 2, 80
+    q, k, v = _cpu_rand(B, Hq, 1, D), _cpu_rand(B, Hkv, S, D), _cpu_rand(B, Hkv, S, D)
+    seq_lens = torch.tensor([S, 33], dtype=torch.int32)
+    starts = torch.tensor([0, 7], dtype=torch.int32)  # row 1 is left-padded
+    scale = 1.0 / math.sqrt(D)
+    want = ops.attention_decode(q.float(), k.float(), v.float(), seq_lens, scale,
+                                seq_starts=starts)
+    out = ops.attention_decode(q.to(DEV), k.to(DEV), v.to(DEV), seq_lens.to(DEV), scale,
+                               seq_starts=starts.to(DEV))
+    torch.testing.assert_close(out.float().cpu(), want, atol=3e-2, rtol=0)
+
+
+_FUSED_MODES = ("alibi", "rope_interleaved", "rope")
+_FUSED_ELSEWHERE = {(64, "alibi"), (128, "alibi"), (96, "rope")}
+
+
+def _fused_decode_reference(qkv, kc, vc, seq_lens, key_starts, idx, mode, scale):
+    """Eager split + reference RoPE over the first D/2 dims at position
+    idx - key_start (ALiBi: no rotation, slopes in the attention) + cache
+    append + the CPU attention_decode reference.  All on the CPU."""
+    B, H, S, D = kc.shape
+    rot = 0 if mode == "alibi" else D // 2
+    parts = qkv.view(B, 3, H, 1, D)
+    qr, knew = parts[:, 0].clone(), parts[:, 1].clone()  # [B, H, 1, D]
+    if rot:
+        cos, sin = reference.rope_cos_sin(S, rot)
+        for b in range(B):
+            p = idx - int(key_starts[b])
+            qb, kb = reference.apply_rope(qr[b:b + 1, ..., :rot], knew[b:b + 1, ..., :rot],
+                                          cos[p:p + 1], sin[p:p + 1],
+                                          interleaved=mode == "rope_interleaved")
+            qr[b:b + 1, ..., :rot], knew[b:b + 1, ..., :rot] = qb, kb
+    kr, vr = kc.clone(), vc.clone()
+    kr[:, :, idx] = knew[:, :, 0]
+    vr[:, :, idx] = parts[:, 2, :, 0]
+    want = ops.attention_decode(qr.float(), kr.float(), vr.float(), seq_lens, scale,
+                                seq_starts=key_starts,
+                                alibi_slopes=alibi_slopes(H) if mode == "alibi" else None)
+    return want, kr, vr, rot
+
+
+def _fused_decode_case(D, mode):
+    """CPU inputs and reference of one case; shows on the reference alone that
+    a kernel of another mode could not pass (each moves it past the tolerance)."""
+    torch.manual_seed(9)
+    B, H, S, idx = 2, 4, 80, 70
+    qkv = _cpu_rand(B, 1, 3 * H * D)
+    kc, vc = torch.zeros(B, H, S, D).bfloat16(), torch.zeros(B, H, S, D).bfloat16()
+    kc[:, :, :idx], vc[:, :, :idx] = _cpu_rand(B, H, idx, D), _cpu_rand(B, H, idx, D)
+    seq_lens = torch.full((B,), idx + 1, dtype=torch.int32)
+    key_starts = torch.tensor([0, 5], dtype=torch.int32)  # row 1 is left-padded
+    args = (qkv, kc, vc, seq_lens, key_starts, idx)
+    scale = 1.0 / math.sqrt(D)
+    want, kr, vr, rot = _fused_decode_reference(*args, mode, scale)
+    for other in _FUSED_MODES:
+        if other != mode:
+            moved = (_fused_decode_reference(*args, other, scale)[0] - want).abs().max().item()
+            assert moved > 3e-2, f"mode {other} moves the reference by {moved:.3g}"
+    return args, scale, rot, want, kr, vr
+
+
+@pytest.mark.parametrize("D,mode", [(D, m) for D in (32, 64, 96, 128, 256) for m in _FUSED_MODES
+                                    if (D, m) not in _FUSED_ELSEWHERE])
+def test_fused_decode_attention_every_mode(D, mode):
+    (qkv, kc, vc, seq_lens, key_starts, idx), scale, rot, want, kr, vr = _fused_decode_case(D, mode)
+    B, H, S, _ = kc.shape
+    cos, sin = reference.rope_cos_sin(S, rot, device=DEV) if rot else (None, None)
+    kg, vg = kc.to(DEV), vc.to(DEV)
+    out = ops.fused_decode_attention(
+        qkv.to(DEV), kg, vg, seq_lens.to(DEV), key_starts.to(DEV), cos, sin,
+        torch.tensor([idx], dtype=torch.long, device=DEV), rot, mode == "rope_interleaved", scale,
+        alibi_slopes=alibi_slopes(H).to(DEV) if mode == "alibi" else None)
+    assert out.shape == (B, H, 1, D)
+    torch.testing.assert_close(out.float().cpu(), want, atol=3e-2, rtol=0)
+    # appended rows: V and the unrotated K dims are copies, bit for bit; the
+    # rotated K dims agree to one bf16 ulp (see test_fused_decode_attention_d96_rope)
+    assert torch.equal(vg.cpu(), vr)
+    assert torch.equal(kg.cpu()[..., rot:], kr[..., rot:])
+    torch.testing.assert_close(kg.cpu()[:, :, idx, :rot].float(), kr[:, :, idx, :rot].float(),
+                               atol=2.0 ** -10, rtol=2.0 ** -8)
+
+
+# --------------------------------------------------------------------------
 # tiny NeoX-shaped (D=96) and GPT-J-shaped (D=256) models
 # --------------------------------------------------------------------------
 

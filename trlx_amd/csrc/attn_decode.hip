@@ -9,6 +9,7 @@
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
 
+#include "attn_host.h"
 #include "common.h"
 
 namespace {
@@ -319,13 +320,8 @@ at::Tensor fused_decode_attention(const at::Tensor& qkv, at::Tensor& kcache, at:
     cs = cos->data_ptr<float>();
     sn = sin->data_ptr<float>();
   }
-  const int* ss = nullptr;
-  at::Tensor ssc;
-  if (seq_starts.has_value()) {
-    ssc = seq_starts->contiguous();
-    TORCH_CHECK(ssc.numel() == B && ssc.dtype() == at::kInt);
-    ss = ssc.data_ptr<int>();
-  }
+  const auto ss_t = optional_int_ptr(seq_starts, qkv, B, "fused_decode_attention", "seq_starts");
+  const int* ss = ss_t.second;
   auto stream = c10::hip::getCurrentHIPStream();
   const int grid = B * Hkv;
   auto qp = reinterpret_cast<const bf16_t*>(qkv.data_ptr());
@@ -334,27 +330,17 @@ at::Tensor fused_decode_attention(const at::Tensor& qkv, at::Tensor& kcache, at:
   auto op = reinterpret_cast<bf16_t*>(out.data_ptr());
   auto sl = seq_lens.data_ptr<int>();
   auto ci = cache_idx.data_ptr<long>();
-#define LAUNCH_FUSED(DV)                                                           \
-  do {                                                                             \
-    if (asl != nullptr) /* no RoPE on this branch (checked above) */               \
-      fused_decode_attn_kernel<DV, false, true><<<grid, BLOCK, 0, stream>>>(       \
-          qp, kp, vp, sl, ss, cs, sn, ci, asl, op, Hkv, S, (int)rot, (float)scale); \
-    else if (interleaved)                                                          \
-      fused_decode_attn_kernel<DV, true, false><<<grid, BLOCK, 0, stream>>>(       \
-          qp, kp, vp, sl, ss, cs, sn, ci, asl, op, Hkv, S, (int)rot, (float)scale); \
-    else                                                                           \
-      fused_decode_attn_kernel<DV, false, false><<<grid, BLOCK, 0, stream>>>(      \
-          qp, kp, vp, sl, ss, cs, sn, ci, asl, op, Hkv, S, (int)rot, (float)scale); \
-  } while (0)
-  switch (D) {
-    case 32: LAUNCH_FUSED(32); break;
-    case 64: LAUNCH_FUSED(64); break;
-    case 96: LAUNCH_FUSED(96); break;
-    case 128: LAUNCH_FUSED(128); break;
-    case 256: LAUNCH_FUSED(256); break;
-    default: TORCH_CHECK(false, "fused_decode_attention: head dim must be 32/64/96/128/256");
-  }
-#undef LAUNCH_FUSED
+  dispatch_head_dim(kDecodeHeadDims, D, "fused_decode_attention", [&](auto d) {
+    auto launch = [&](auto il, auto al) {
+      fused_decode_attn_kernel<decltype(d)::value, decltype(il)::value, decltype(al)::value>
+          <<<grid, BLOCK, 0, stream>>>(qp, kp, vp, sl, ss, cs, sn, ci, asl, op, Hkv, S, (int)rot,
+                                       (float)scale);
+    };
+    // three-way: ALiBi has no RoPE (checked above), so no interleaved variant
+    if (asl != nullptr) launch(std::false_type{}, std::true_type{});
+    else if (interleaved) launch(std::true_type{}, std::false_type{});
+    else launch(std::false_type{}, std::false_type{});
+  });
   HIP_CHECK_LAST();
   return out;
 }
@@ -380,32 +366,14 @@ at::Tensor attention_decode(const at::Tensor& q, const at::Tensor& kc, const at:
   auto vp = reinterpret_cast<const bf16_t*>(vc.data_ptr());
   auto op = reinterpret_cast<bf16_t*>(out.data_ptr());
   auto sl = seq_lens.data_ptr<int>();
-  const int* ss = nullptr;
-  at::Tensor ssc;
-  if (seq_starts.has_value()) {
-    ssc = seq_starts->contiguous();
-    TORCH_CHECK(ssc.numel() == B && ssc.dtype() == at::kInt);
-    ss = ssc.data_ptr<int>();
-  }
-#define LAUNCH_DECODE(DV)                                                                  \
-  do {                                                                                     \
-    if (asl != nullptr)                                                                    \
-      attn_decode_kernel<DV, true><<<grid, BLOCK, 0, stream>>>(qp, kp, vp, sl, ss, asl, op, \
-                                                               Hq, Hkv, S, (float)scale);  \
-    else                                                                                   \
-      attn_decode_kernel<DV, false><<<grid, BLOCK, 0, stream>>>(qp, kp, vp, sl, ss, asl, op, \
-                                                                Hq, Hkv, S, (float)scale); \
-  } while (0)
-  switch (D) {
-    case 32: LAUNCH_DECODE(32); break;
-    case 64: LAUNCH_DECODE(64); break;
-    case 96: LAUNCH_DECODE(96); break;
-    case 128: LAUNCH_DECODE(128); break;
-    case 256: LAUNCH_DECODE(256); break;
-    default:
-      TORCH_CHECK(false, "attention_decode: head dim must be 32/64/96/128/256, got ", D);
-  }
-#undef LAUNCH_DECODE
+  const auto ss_t = optional_int_ptr(seq_starts, q, B, "attention_decode", "seq_starts");
+  const int* ss = ss_t.second;
+  dispatch_head_dim(kDecodeHeadDims, D, "attention_decode", [&](auto d) {
+    dispatch_bool(asl != nullptr, [&](auto al) {
+      attn_decode_kernel<decltype(d)::value, decltype(al)::value><<<grid, BLOCK, 0, stream>>>(
+          qp, kp, vp, sl, ss, asl, op, Hq, Hkv, S, (float)scale);
+    });
+  });
   HIP_CHECK_LAST();
   return out;
 }

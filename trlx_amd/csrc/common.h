@@ -193,6 +193,10 @@ DEV float alibi_score(float score, float slope, int key, int kstart) {
 // this one helper, so the backward's recomputed P matches the saved logsumexp.
 // Lanes that stand for rows >= Tq or keys >= Tk (masked later) compute an
 // index outside [0, L): the index is clamped BEFORE the load, never after.
+// The lines around the call (add ALiBi / this bias, then test visibility) are
+// written out three times in the kernels on purpose: moving them into a shared
+// helper changed the SGPR allocation of the existing instantiations
+// (profiles/t5_attention_notes.md §1).
 DEV float rel_bias_score(float score, const float* __restrict__ bias_row, int L, int key,
                          int qpos, int bias_zero) {
   const int idx = min(max(key - qpos + bias_zero, 0), L - 1);
@@ -241,75 +245,6 @@ inline unsigned long long splitmix64_host(unsigned long long z) {
   z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
   z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
   return z ^ (z >> 31);
-}
-
-// host side: validate an optional ALiBi slope vector (fp32, contiguous, same
-// device as `like`, one slope per QUERY head) and return its pointer, or null
-// when no bias was given.  (every kernel file includes ATen before common.h)
-inline const float* alibi_slopes_ptr(const c10::optional<at::Tensor>& slopes,
-                                     const at::Tensor& like, long num_q_heads,
-                                     const char* op) {
-  if (!slopes.has_value()) return nullptr;
-  TORCH_CHECK(slopes->dtype() == at::kFloat && slopes->is_contiguous(), op,
-              ": alibi_slopes must be contiguous fp32");
-  TORCH_CHECK(slopes->device() == like.device(), op,
-              ": alibi_slopes must live on the same device as the inputs");
-  TORCH_CHECK(slopes->numel() == num_q_heads, op, ": alibi_slopes needs one slope per query head (",
-              num_q_heads, "), got ", slopes->numel());
-  return slopes->data_ptr<float>();
-}
-
-// host side: the seq2seq (T5) modes of the flash kernels — non-causal,
-// Toeplitz relative bias, arbitrary key mask.  Validates the optional inputs
-// and returns raw pointers (null = mode off).  `any` says whether a seq2seq
-// instantiation is needed at all; those exist at head dims 64 and 128 only.
-struct Seq2SeqArgs {
-  const float* rel_bias = nullptr;  // [Hq, L] fp32
-  int bias_len = 0;                 // L
-  int bias_zero = 0;                // index of relative position 0
-  const unsigned char* key_mask = nullptr;  // [B, Tk], nonzero = visible
-  bool any = false;
-};
-
-inline Seq2SeqArgs seq2seq_args(const c10::optional<at::Tensor>& rel_bias, long bias_zero,
-                                const c10::optional<at::Tensor>& key_mask, bool causal,
-                                bool has_key_starts, bool has_alibi, const at::Tensor& like,
-                                long B, long num_q_heads, long Tq, long Tk, long start_pos,
-                                long D, const char* op) {
-  Seq2SeqArgs a;
-  if (rel_bias.has_value()) {
-    TORCH_CHECK(!has_alibi, op, ": rel_bias and alibi_slopes are mutually exclusive");
-    TORCH_CHECK(rel_bias->dtype() == at::kFloat && rel_bias->is_contiguous() &&
-                    rel_bias->dim() == 2 && rel_bias->size(0) == num_q_heads,
-                op, ": rel_bias must be contiguous fp32 [Hq, L]");
-    TORCH_CHECK(rel_bias->device() == like.device(), op,
-                ": rel_bias must live on the same device as the inputs");
-    const long L = rel_bias->size(1);
-    TORCH_CHECK(bias_zero - (start_pos + Tq - 1) >= 0 && bias_zero + Tk - 1 < L, op,
-                ": rel_bias [Hq, ", L, "] with bias_zero ", bias_zero,
-                " does not cover queries ", start_pos, "..", start_pos + Tq - 1, " x keys 0..",
-                Tk - 1);
-    a.rel_bias = rel_bias->data_ptr<float>();
-    a.bias_len = (int)L;
-    a.bias_zero = (int)bias_zero;
-  }
-  if (key_mask.has_value()) {
-    TORCH_CHECK(!has_key_starts, op, ": key_mask and key_starts are mutually exclusive");
-    TORCH_CHECK(key_mask->dtype() == at::kByte && key_mask->is_contiguous() &&
-                    key_mask->dim() == 2 && key_mask->size(0) == B && key_mask->size(1) == Tk,
-                op, ": key_mask must be contiguous uint8 [B, Tk]");
-    TORCH_CHECK(key_mask->device() == like.device(), op,
-                ": key_mask must live on the same device as the inputs");
-    TORCH_CHECK(Tk > 0, op, ": key_mask needs at least one key");
-    a.key_mask = key_mask->data_ptr<unsigned char>();
-  }
-  a.any = a.rel_bias != nullptr || a.key_mask != nullptr || !causal;
-  if (a.any) {
-    TORCH_CHECK(!has_alibi, op, ": key_mask / non-causal attention do not combine with alibi_slopes");
-    TORCH_CHECK(D == 64 || D == 128, op,
-                ": rel_bias / key_mask / non-causal attention need head dim 64 or 128, got ", D);
-  }
-  return a;
 }
 
 #define HIP_CHECK_LAST()                                          \

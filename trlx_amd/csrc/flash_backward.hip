@@ -46,6 +46,7 @@
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
 
+#include "attn_host.h"
 #include "common.h"
 
 namespace {
@@ -427,17 +428,13 @@ std::vector<at::Tensor> flash_prefill_bwd(const at::Tensor& q, const at::Tensor&
   const Seq2SeqArgs s2s =
       seq2seq_args(rel_bias, bias_zero, key_mask, causal, key_starts.has_value(), sl != nullptr,
                    q, B, Hq, T, Tk, 0, D, "flash_prefill_bwd");
+  const auto ks_t = optional_int_ptr(key_starts, q, B, "flash_prefill_bwd", "key_starts");
+  const int* ks = ks_t.second;
   auto dq = at::empty_like(q);
   auto dk = at::empty_like(k);
   auto dv = at::empty_like(v);
   auto dc = dout.contiguous();
   auto drow = (dc.to(at::kFloat) * out.to(at::kFloat)).sum(-1).contiguous();  // [B,Hq,T]
-  const int* ks = nullptr;
-  at::Tensor ksc;
-  if (key_starts.has_value()) {
-    ksc = key_starts->contiguous();
-    ks = ksc.data_ptr<int>();
-  }
   auto stream = c10::hip::getCurrentHIPStream();
   auto qp = reinterpret_cast<const bf16_t*>(q.data_ptr());
   auto kp = reinterpret_cast<const bf16_t*>(k.data_ptr());
@@ -446,65 +443,27 @@ std::vector<at::Tensor> flash_prefill_bwd(const at::Tensor& q, const at::Tensor&
   auto dqp = reinterpret_cast<bf16_t*>(dq.data_ptr());
   auto dkp = reinterpret_cast<bf16_t*>(dk.data_ptr());
   auto dvp = reinterpret_cast<bf16_t*>(dv.data_ptr());
+  const float* lp = lse.data_ptr<float>();
+  const float* drp = drow.data_ptr<float>();
   dim3 gk((Tk + BT - 1) / BT, Hkv, B);
   dim3 gq((T + BT - 1) / BT, Hq, B);
-#define LAUNCH_BWD(DV, AL)                                                                \
-  do {                                                                                    \
-    flash_bwd_dkv_kernel<DV, AL><<<gk, BBLOCK, 0, stream>>>(                              \
-        qp, kp, vp, dop, lse.data_ptr<float>(), drow.data_ptr<float>(), ks, sl, dkp, dvp, \
-        B, Hq, Hkv, T, (float)scale);                                                     \
-    flash_bwd_dq_kernel<DV, AL><<<gq, BBLOCK, 0, stream>>>(                               \
-        qp, kp, vp, dop, lse.data_ptr<float>(), drow.data_ptr<float>(), ks, sl, dqp, B,   \
-        Hq, Hkv, T, (float)scale);                                                        \
-  } while (0)
-#define LAUNCH_S2S(DV, CA, RB, KM)                                                        \
-  do {                                                                                    \
-    flash_bwd_dkv_kernel<DV, false, CA, RB, KM><<<gk, BBLOCK, 0, stream>>>(               \
-        qp, kp, vp, dop, lse.data_ptr<float>(), drow.data_ptr<float>(), ks, sl, dkp, dvp, \
-        B, Hq, Hkv, T, (float)scale, s2s.rel_bias, s2s.bias_len, s2s.bias_zero,           \
-        s2s.key_mask, Tk);                                                                \
-    flash_bwd_dq_kernel<DV, false, CA, RB, KM><<<gq, BBLOCK, 0, stream>>>(                \
-        qp, kp, vp, dop, lse.data_ptr<float>(), drow.data_ptr<float>(), ks, sl, dqp, B,   \
-        Hq, Hkv, T, (float)scale, s2s.rel_bias, s2s.bias_len, s2s.bias_zero,              \
-        s2s.key_mask, Tk);                                                                \
-  } while (0)
-  // seq2seq modes (head dims 64 / 128, checked in seq2seq_args): one
-  // instantiation per (causal, bias, mask) combination
-#define LAUNCH_BWD_S2S(DV)                                                                \
-  do {                                                                                    \
-    const bool rb = s2s.rel_bias != nullptr, km = s2s.key_mask != nullptr;                \
-    if (causal) {                                                                         \
-      if (rb && km) LAUNCH_S2S(DV, true, true, true);                                     \
-      else if (rb) LAUNCH_S2S(DV, true, true, false);                                     \
-      else LAUNCH_S2S(DV, true, false, true);                                             \
-    } else {                                                                              \
-      if (rb && km) LAUNCH_S2S(DV, false, true, true);                                    \
-      else if (rb) LAUNCH_S2S(DV, false, true, false);                                    \
-      else if (km) LAUNCH_S2S(DV, false, false, true);                                    \
-      else LAUNCH_S2S(DV, false, false, false);                                           \
-    }                                                                                     \
-  } while (0)
-  if (s2s.any) {
-    if (D == 64) LAUNCH_BWD_S2S(64); else LAUNCH_BWD_S2S(128);
-  } else
-  switch (D) {
-    case 64:
-      if (sl != nullptr) LAUNCH_BWD(64, true); else LAUNCH_BWD(64, false);
-      break;
-    case 96:
-      if (sl != nullptr) LAUNCH_BWD(96, true); else LAUNCH_BWD(96, false);
-      break;
-    case 128:
-      if (sl != nullptr) LAUNCH_BWD(128, true); else LAUNCH_BWD(128, false);
-      break;
-    case 256:
-      if (sl != nullptr) LAUNCH_BWD(256, true); else LAUNCH_BWD(256, false);
-      break;
-    default: TORCH_CHECK(false, "flash_prefill_bwd: head dim must be 64, 96, 128 or 256");
-  }
-#undef LAUNCH_BWD_S2S
-#undef LAUNCH_S2S
-#undef LAUNCH_BWD
+  dispatch_flash_mode(
+      D, sl != nullptr, s2s.any, causal, s2s.rel_bias != nullptr, s2s.key_mask != nullptr,
+      "flash_prefill_bwd", [&](auto d, auto al, auto ca, auto rb, auto km) {
+        constexpr int DV = decltype(d)::value;
+        constexpr bool AL = decltype(al)::value, CA = decltype(ca)::value,
+                       RB = decltype(rb)::value, KM = decltype(km)::value;
+        // both kernels end in the same optional seq2seq pack
+        auto launch = [&](auto... s2s_pack) {
+          flash_bwd_dkv_kernel<DV, AL, CA, RB, KM><<<gk, BBLOCK, 0, stream>>>(
+              qp, kp, vp, dop, lp, drp, ks, sl, dkp, dvp, B, Hq, Hkv, T, (float)scale,
+              s2s_pack...);
+          flash_bwd_dq_kernel<DV, AL, CA, RB, KM><<<gq, BBLOCK, 0, stream>>>(
+              qp, kp, vp, dop, lp, drp, ks, sl, dqp, B, Hq, Hkv, T, (float)scale, s2s_pack...);
+        };
+        if constexpr (CA && !RB && !KM) launch();
+        else launch(s2s.rel_bias, s2s.bias_len, s2s.bias_zero, s2s.key_mask, Tk);
+      });
   HIP_CHECK_LAST();
   return {dq, dk, dv};
 }

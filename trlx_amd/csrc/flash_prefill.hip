@@ -42,6 +42,7 @@
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
 
+#include "attn_host.h"
 #include "common.h"
 
 namespace {
@@ -354,13 +355,8 @@ std::vector<at::Tensor> flash_prefill_lse(const at::Tensor& q, const at::Tensor&
   auto out = at::empty_like(q);
   auto lse = want_lse ? at::empty({B, Hq, T}, q.options().dtype(at::kFloat)) : at::Tensor();
   if (q.numel() == 0) return {out, lse};
-  const int* ks = nullptr;
-  at::Tensor ksc;
-  if (key_starts.has_value()) {
-    ksc = key_starts->contiguous();
-    TORCH_CHECK(ksc.numel() == B && ksc.dtype() == at::kInt);
-    ks = ksc.data_ptr<int>();
-  }
+  const auto ks_t = optional_int_ptr(key_starts, q, B, "flash_prefill", "key_starts");
+  const int* ks = ks_t.second;
   auto stream = c10::hip::getCurrentHIPStream();
   dim3 grid((T + TQ - 1) / TQ, Hq, B);
   auto qp = reinterpret_cast<const bf16_t*>(q.data_ptr());
@@ -368,51 +364,20 @@ std::vector<at::Tensor> flash_prefill_lse(const at::Tensor& q, const at::Tensor&
   auto vp = reinterpret_cast<const bf16_t*>(v.data_ptr());
   auto op = reinterpret_cast<bf16_t*>(out.data_ptr());
   float* lp = want_lse ? lse.data_ptr<float>() : nullptr;
-#define LAUNCH_FWD(DV, AL)                                                              \
-  flash_prefill_kernel<DV, AL><<<grid, FBLOCK, 0, stream>>>(                            \
-      qp, kp, vp, ks, sl, op, lp, B, Hq, Hkv, T, Tk, Sk, (int)start_pos, (float)scale)
-#define LAUNCH_S2S(DV, CA, RB, KM)                                                       \
-  flash_prefill_kernel<DV, false, CA, RB, KM><<<grid, FBLOCK, 0, stream>>>(              \
-      qp, kp, vp, ks, sl, op, lp, B, Hq, Hkv, T, Tk, Sk, (int)start_pos, (float)scale,   \
-      s2s.rel_bias, s2s.bias_len, s2s.bias_zero, s2s.key_mask)
-  // seq2seq modes (head dims 64 / 128, checked in seq2seq_args): one
-  // instantiation per (causal, bias, mask) combination
-#define LAUNCH_FWD_S2S(DV)                                                               \
-  do {                                                                                   \
-    const bool rb = s2s.rel_bias != nullptr, km = s2s.key_mask != nullptr;               \
-    if (causal) {                                                                        \
-      if (rb && km) LAUNCH_S2S(DV, true, true, true);                                    \
-      else if (rb) LAUNCH_S2S(DV, true, true, false);                                    \
-      else LAUNCH_S2S(DV, true, false, true);                                            \
-    } else {                                                                             \
-      if (rb && km) LAUNCH_S2S(DV, false, true, true);                                   \
-      else if (rb) LAUNCH_S2S(DV, false, true, false);                                   \
-      else if (km) LAUNCH_S2S(DV, false, false, true);                                   \
-      else LAUNCH_S2S(DV, false, false, false);                                          \
-    }                                                                                    \
-  } while (0)
-  if (s2s.any) {
-    if (D == 64) LAUNCH_FWD_S2S(64); else LAUNCH_FWD_S2S(128);
-  } else
-  switch (D) {
-    case 64:
-      if (sl != nullptr) LAUNCH_FWD(64, true); else LAUNCH_FWD(64, false);
-      break;
-    case 96:
-      if (sl != nullptr) LAUNCH_FWD(96, true); else LAUNCH_FWD(96, false);
-      break;
-    case 128:
-      if (sl != nullptr) LAUNCH_FWD(128, true); else LAUNCH_FWD(128, false);
-      break;
-    case 256:
-      if (sl != nullptr) LAUNCH_FWD(256, true); else LAUNCH_FWD(256, false);
-      break;
-    default:
-      TORCH_CHECK(false, "flash_prefill: head dim must be 64, 96, 128 or 256, got ", D);
-  }
-#undef LAUNCH_FWD_S2S
-#undef LAUNCH_S2S
-#undef LAUNCH_FWD
+  dispatch_flash_mode(
+      D, sl != nullptr, s2s.any, causal, s2s.rel_bias != nullptr, s2s.key_mask != nullptr,
+      "flash_prefill", [&](auto d, auto al, auto ca, auto rb, auto km) {
+        constexpr int DV = decltype(d)::value;
+        constexpr bool AL = decltype(al)::value, CA = decltype(ca)::value,
+                       RB = decltype(rb)::value, KM = decltype(km)::value;
+        auto launch = [&](auto... s2s_pack) {
+          flash_prefill_kernel<DV, AL, CA, RB, KM><<<grid, FBLOCK, 0, stream>>>(
+              qp, kp, vp, ks, sl, op, lp, B, Hq, Hkv, T, Tk, Sk, (int)start_pos, (float)scale,
+              s2s_pack...);
+        };
+        if constexpr (CA && !RB && !KM) launch();
+        else launch(s2s.rel_bias, s2s.bias_len, s2s.bias_zero, s2s.key_mask);
+      });
   HIP_CHECK_LAST();
   return {out, lse};
 }

@@ -178,6 +178,9 @@ class Attention(nn.Module):
         # under sequence parallelism the projection gathers the full sequence
         T = qkv.shape[1]
 
+        def project(out):  # attention output [B, H, T, D] -> o_proj of [B, T, H*D]
+            return dense(self.o_proj, out.transpose(1, 2).reshape(B, T, -1))
+
         # fused single-token decode path: decode_prep (split+RoPE+cache
         # append) + flash-decode attention, fully device-side (hipGraph-safe)
         if (T == 1 and kv_cache is not None and ctx.cache_idx is not None
@@ -204,7 +207,7 @@ class Attention(nn.Module):
                                            kv_cache.v[self.layer_idx],
                                            ctx.seq_lens, self.scale, seq_starts=ctx.key_starts,
                                            alibi_slopes=ctx.alibi_slopes)
-            return dense(self.o_proj, out.transpose(1, 2).reshape(B, T, -1))
+            return project(out)
 
         if x.is_cuda and x.dtype == torch.bfloat16 and ops.extension_available():
             # fused split + RoPE + q-scale (one kernel fwd, one bwd)
@@ -239,11 +242,14 @@ class Attention(nn.Module):
             k = k.scatter(2, idx, pk.unsqueeze(0).expand(B_, -1, -1, -1))
             v = v.scatter(2, idx, pv.unsqueeze(0).expand(B_, -1, -1, -1))
 
-        flash_ok = (
+        # what both flash directions need; each adds its grad mode and gate
+        flash_common = (
             T > 1 and x.is_cuda and q.dtype == torch.bfloat16
-            and not torch.is_grad_enabled()
             and (self.attn_pdrop == 0 or not self.training)
             and ops.extension_available()
+        )
+        flash_ok = (
+            flash_common and not torch.is_grad_enabled()
             # head dim + TRLX_AMD_NO_FLASH_PREFILL, per the measured defaults
             and ops.flash_enabled(self.head_dim, train=False)
         )
@@ -264,16 +270,14 @@ class Attention(nn.Module):
                                            1.0 if pre_scaled else self.scale,
                                            seq_starts=ctx.key_starts,
                                            alibi_slopes=ctx.alibi_slopes)
-                out = out.transpose(1, 2).reshape(B, T, -1)
-                return dense(self.o_proj, out)
+                return project(out)
             if flash_ok:
                 # cache prefill through the flash kernel: reads the cache
                 # tensors in place (allocated stride Sk, valid start_pos+T)
                 out = ops.flash_prefill(q, k_full, v_full, ctx.key_starts, ctx.start_pos,
                                         1.0 if pre_scaled else self.scale,
                                         tk=ctx.start_pos + T, alibi_slopes=ctx.alibi_slopes)
-                out = out.transpose(1, 2).reshape(B, T, -1)
-                return dense(self.o_proj, out)
+                return project(out)
             k = k_full[:, :, : ctx.start_pos + T]
             v = v_full[:, :, : ctx.start_pos + T]
         elif flash_ok:
@@ -284,14 +288,10 @@ class Attention(nn.Module):
                                     ctx.key_starts, ctx.start_pos,
                                     1.0 if pre_scaled else self.scale,
                                     alibi_slopes=ctx.alibi_slopes)
-            out = out.transpose(1, 2).reshape(B, T, -1)
-            return dense(self.o_proj, out)
+            return project(out)
 
         flash_train_ok = (
-            T > 1 and x.is_cuda and q.dtype == torch.bfloat16
-            and torch.is_grad_enabled() and kv_cache is None and ctx.start_pos == 0
-            and (self.attn_pdrop == 0 or not self.training)
-            and ops.extension_available()
+            flash_common and torch.is_grad_enabled() and kv_cache is None and ctx.start_pos == 0
             # head dim + TRLX_AMD_NO_FLASH_PREFILL / TRLX_AMD_NO_FLASH_TRAIN
             and ops.flash_enabled(self.head_dim, train=True)
         )
@@ -303,8 +303,7 @@ class Attention(nn.Module):
             out = ops.flash_attention(q, k, v, ctx.key_starts,
                                       1.0 if pre_scaled else self.scale,
                                       alibi_slopes=ctx.alibi_slopes)
-            out = out.transpose(1, 2).reshape(B, T, -1)
-            return dense(self.o_proj, out)
+            return project(out)
 
         # prefill / training: rocBLAS batched GEMMs + fused causal softmax
         if self.num_kv_heads != self.num_heads:
@@ -321,8 +320,7 @@ class Attention(nn.Module):
         if self.attn_pdrop > 0 and self.training:
             probs = F.dropout(probs, self.attn_pdrop)
         out = torch.matmul(probs, v)
-        out = out.transpose(1, 2).reshape(B, T, -1)
-        return dense(self.o_proj, out)
+        return project(out)
 
 
 def dense(lin, x, act_code=0, act_fn=None):

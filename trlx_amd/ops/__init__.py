@@ -18,8 +18,7 @@ from . import reference
 
 # Head dims the attention kernels are instantiated for — the one source of
 # truth for every dispatch gate (models/nn/transformer.py, generation.py); the
-# switch (D) blocks in csrc/flash_prefill.hip, flash_backward.hip and
-# attn_decode.hip list the same sets.
+# head-dim lists at the top of csrc/attn_host.h are the same sets.
 FLASH_HEAD_DIMS = (64, 96, 128, 256)  # flash_prefill / flash_attention (fwd + bwd)
 DECODE_HEAD_DIMS = (32, 64, 96, 128, 256)  # attention_decode / fused_decode_attention
 
@@ -33,28 +32,6 @@ DECODE_HEAD_DIMS = (32, 64, 96, 128, 256)  # attention_decode / fused_decode_att
 FLASH_PREFILL_DEFAULT_DIMS = (64, 96, 128)
 FLASH_TRAIN_DEFAULT_DIMS = (64, 128)
 
-
-def flash_enabled(head_dim: int, train: bool) -> bool:
-    """Does a model with this head dim take the flash kernels for the no_grad
-    forward (``train=False``) or the training forward+backward (``train=True``)?
-
-    ``TRLX_AMD_NO_FLASH_PREFILL=1`` turns both directions off and
-    ``TRLX_AMD_NO_FLASH_TRAIN=1`` the training direction; ``=0`` turns the
-    direction on for every instantiated head dim; unset follows the measured
-    defaults above."""
-    if head_dim not in FLASH_HEAD_DIMS:
-        return False
-    prefill = os.environ.get("TRLX_AMD_NO_FLASH_PREFILL")
-    if prefill == "1":
-        return False
-    if not train:
-        return prefill == "0" or head_dim in FLASH_PREFILL_DEFAULT_DIMS
-    switch = os.environ.get("TRLX_AMD_NO_FLASH_TRAIN")
-    if switch == "1":
-        return False
-    return switch == "0" or head_dim in FLASH_TRAIN_DEFAULT_DIMS
-
-
 # The seq2seq (T5) modes of the same kernels — non-causal, Toeplitz relative
 # bias, arbitrary key mask, Tq != Tk — exist at these head dims only (t5-small
 # through 11b and flan-t5).  Their defaults follow the same rule, measured by
@@ -67,21 +44,40 @@ SEQ2SEQ_FLASH_PREFILL_DEFAULT_DIMS = (64, 128)
 SEQ2SEQ_FLASH_TRAIN_DEFAULT_DIMS = (64, 128)
 
 
-def seq2seq_flash_enabled(head_dim: int, train: bool) -> bool:
-    """``flash_enabled`` for the T5 attention path (``ops.seq2seq_attention``):
-    the same two switches with the same meaning (``1`` off, ``0`` on, unset
-    follows the measured defaults), over the seq2seq default sets."""
-    if head_dim not in SEQ2SEQ_FLASH_HEAD_DIMS:
+def _flash_gate(head_dim: int, train: bool, built, prefill_default, train_default) -> bool:
+    """The gate behind ``flash_enabled`` / ``seq2seq_flash_enabled``: ``built``
+    are the instantiated head dims, the other two the measured defaults."""
+    if head_dim not in built:
         return False
     prefill = os.environ.get("TRLX_AMD_NO_FLASH_PREFILL")
     if prefill == "1":
         return False
     if not train:
-        return prefill == "0" or head_dim in SEQ2SEQ_FLASH_PREFILL_DEFAULT_DIMS
+        return prefill == "0" or head_dim in prefill_default
     switch = os.environ.get("TRLX_AMD_NO_FLASH_TRAIN")
     if switch == "1":
         return False
-    return switch == "0" or head_dim in SEQ2SEQ_FLASH_TRAIN_DEFAULT_DIMS
+    return switch == "0" or head_dim in train_default
+
+
+def flash_enabled(head_dim: int, train: bool) -> bool:
+    """Does a model with this head dim take the flash kernels for the no_grad
+    forward (``train=False``) or the training forward+backward (``train=True``)?
+
+    ``TRLX_AMD_NO_FLASH_PREFILL=1`` turns both directions off and
+    ``TRLX_AMD_NO_FLASH_TRAIN=1`` the training direction; ``=0`` turns the
+    direction on for every instantiated head dim; unset follows the measured
+    defaults above."""
+    return _flash_gate(head_dim, train, FLASH_HEAD_DIMS, FLASH_PREFILL_DEFAULT_DIMS,
+                       FLASH_TRAIN_DEFAULT_DIMS)
+
+
+def seq2seq_flash_enabled(head_dim: int, train: bool) -> bool:
+    """``flash_enabled`` for the T5 attention path (``ops.seq2seq_attention``):
+    the same two switches with the same meaning (``1`` off, ``0`` on, unset
+    follows the measured defaults), over the seq2seq default sets."""
+    return _flash_gate(head_dim, train, SEQ2SEQ_FLASH_HEAD_DIMS,
+                       SEQ2SEQ_FLASH_PREFILL_DEFAULT_DIMS, SEQ2SEQ_FLASH_TRAIN_DEFAULT_DIMS)
 
 
 _EXT = None
@@ -882,28 +878,31 @@ def flash_prefill(q, k, v, key_starts=None, start_pos: int = 0, scale: float = 1
 
 
 class _FlashAttention(torch.autograd.Function):
-    """Differentiable flash attention (training prefill, start_pos == 0,
-    Tk == T): forward saves the per-row logsumexp, backward recomputes P from
-    it tile-by-tile (csrc/flash_backward.hip) — the [B,H,T,T] scores never
-    materialize in either direction."""
+    """Differentiable flash attention, causal (training prefill: start_pos ==
+    0, Tk == T) and seq2seq alike: forward saves the per-row logsumexp,
+    backward recomputes P from it tile-by-tile (csrc/flash_backward.hip) — the
+    [B,H,T,T] scores never materialize in either direction.  ``alibi_slopes``,
+    ``rel_bias`` and ``key_mask`` are constants here (not trainable; the
+    kernels produce no bias gradient)."""
 
     @staticmethod
-    def forward(ctx, q, k, v, key_starts, scale, ext, alibi_slopes=None):
-        out, lse = ext.flash_prefill_lse(q, k, v, key_starts, 0, float(scale), 0, True,
-                                         alibi_slopes)
+    def forward(ctx, q, k, v, key_starts, alibi_slopes, rel_bias, bias_zero, key_mask, causal,
+                start_pos, scale, ext):
+        out, lse = ext.flash_prefill_lse(q, k, v, key_starts, start_pos, scale, 0, True,
+                                         alibi_slopes, rel_bias, bias_zero, key_mask, causal)
         ctx.save_for_backward(q, k, v, out, lse)
-        ctx.alibi_slopes = alibi_slopes  # constant (not trainable): no grad
-        ctx.key_starts = key_starts
-        ctx.scale = scale
+        # the backward kernels have no start_pos: the bias index is
+        # key - (start_pos + row) + bias_zero, so the offset folds into bias_zero
+        ctx.bwd_args = (key_starts, scale, alibi_slopes, rel_bias, bias_zero - start_pos,
+                        key_mask, causal)
         ctx.ext = ext
         return out
 
     @staticmethod
     def backward(ctx, dout):
         q, k, v, out, lse = ctx.saved_tensors
-        dq, dk, dv = ctx.ext.flash_prefill_bwd(q, k, v, out, dout, lse, ctx.key_starts,
-                                               float(ctx.scale), ctx.alibi_slopes)
-        return dq, dk, dv, None, None, None, None
+        dq, dk, dv = ctx.ext.flash_prefill_bwd(q, k, v, out, dout, lse, *ctx.bwd_args)
+        return (dq, dk, dv) + (None,) * 9
 
 
 def flash_attention(q, k, v, key_starts=None, scale: float = 1.0, alibi_slopes=None):
@@ -917,7 +916,7 @@ def flash_attention(q, k, v, key_starts=None, scale: float = 1.0, alibi_slopes=N
                                        alibi_slopes=alibi_slopes).to(q.dtype)
     ks = key_starts.to(torch.int32).contiguous() if key_starts is not None else None
     return _FlashAttention.apply(q.contiguous(), k.contiguous(), v.contiguous(), ks,
-                                 float(scale), ext, alibi_slopes)
+                                 alibi_slopes, None, 0, None, True, 0, float(scale), ext)
 
 
 # --------------------------------------------------------------------------
@@ -935,33 +934,6 @@ def t5_rel_bias(table: torch.Tensor, q_len: int, k_len: int, q_offset: int = 0,
     with respect to ``table`` (the [num_buckets, H] embedding weight)."""
     return reference.t5_rel_bias(table, q_len, k_len, q_offset, bidirectional, num_buckets,
                                  max_distance)
-
-
-class _Seq2SeqAttention(torch.autograd.Function):
-    """Differentiable seq2seq flash attention: like ``_FlashAttention`` it saves
-    (q, k, v, out, lse) and recomputes P in the backward kernels.  ``rel_bias``
-    and ``key_mask`` are constants here (the kernels produce no bias gradient)."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, rel_bias, bias_zero, key_mask, causal, start_pos, scale, ext):
-        out, lse = ext.flash_prefill_lse(q, k, v, None, start_pos, scale, 0, True, None,
-                                         rel_bias, bias_zero, key_mask, causal)
-        ctx.save_for_backward(q, k, v, out, lse)
-        ctx.rel_bias, ctx.key_mask, ctx.causal = rel_bias, key_mask, causal
-        # the backward kernels have no start_pos: the bias index is
-        # key - (start_pos + row) + bias_zero, so the offset folds into bias_zero
-        ctx.bias_zero = bias_zero - start_pos
-        ctx.scale = scale
-        ctx.ext = ext
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        q, k, v, out, lse = ctx.saved_tensors
-        dq, dk, dv = ctx.ext.flash_prefill_bwd(q, k, v, out, dout, lse, None, ctx.scale, None,
-                                               ctx.rel_bias, ctx.bias_zero, ctx.key_mask,
-                                               ctx.causal)
-        return dq, dk, dv, None, None, None, None, None, None, None
 
 
 def seq2seq_attention(q, k, v, rel_bias=None, bias_zero: int = 0, key_mask=None,
@@ -1002,5 +974,5 @@ def seq2seq_attention(q, k, v, rel_bias=None, bias_zero: int = 0, key_mask=None,
                                  int(bias_zero), km, bool(causal))
     if causal and (start_pos != 0 or q.shape[2] != k.shape[2]):
         raise RuntimeError("seq2seq_attention: causal training needs Tq == Tk and start_pos == 0")
-    return _Seq2SeqAttention.apply(q, k, v, rb, int(bias_zero), km, bool(causal),
-                                   int(start_pos), float(scale), ext)
+    return _FlashAttention.apply(q, k, v, None, None, rb, int(bias_zero), km, bool(causal),
+                                 int(start_pos), float(scale), ext)
