@@ -14,12 +14,13 @@
 
 // The head dims each kernel family is instantiated for: the one place on the
 // C++ side.  ops/__init__.py mirrors them as FLASH_HEAD_DIMS,
-// SEQ2SEQ_FLASH_HEAD_DIMS and DECODE_HEAD_DIMS.
+// SEQ2SEQ_FLASH_HEAD_DIMS, DECODE_HEAD_DIMS and SEQ2SEQ_DECODE_HEAD_DIMS.
 template <int... Ds>
 struct HeadDims {};
 constexpr HeadDims<64, 96, 128, 256> kFlashHeadDims{};       // flash fwd + bwd
 constexpr HeadDims<64, 128> kSeq2SeqFlashHeadDims{};         // their seq2seq modes
 constexpr HeadDims<32, 64, 96, 128, 256> kDecodeHeadDims{};  // attention_decode, fused
+constexpr HeadDims<64, 128> kSeq2SeqDecodeHeadDims{};        // s2s_decode.hip (T5 per-token step)
 
 // ---- runtime value -> compile-time constant ------------------------------------
 

@@ -124,6 +124,15 @@ std::vector<at::Tensor> flash_prefill_bwd(const at::Tensor& q, const at::Tensor&
                                           const c10::optional<at::Tensor>& alibi_slopes,
                                           const c10::optional<at::Tensor>& rel_bias, long bias_zero,
                                           const c10::optional<at::Tensor>& key_mask, bool causal);
+at::Tensor seq2seq_decode_attention(const at::Tensor& q, const at::Tensor& k_new,
+                                    const at::Tensor& v_new, at::Tensor& k_cache,
+                                    at::Tensor& v_cache, const at::Tensor& cache_idx,
+                                    const c10::optional<at::Tensor>& rel_bias, long bias_zero,
+                                    double scale);
+at::Tensor seq2seq_cross_decode_attention(const at::Tensor& q, const at::Tensor& k,
+                                          const at::Tensor& v,
+                                          const c10::optional<at::Tensor>& key_mask,
+                                          double scale);
 void lm_sample_v3(const at::Tensor& x, const at::Tensor& wlm,
                   const c10::optional<at::Tensor>& blm, const at::Tensor& pstats, long nparts,
                   const at::Tensor& nw, const c10::optional<at::Tensor>& nb, at::Tensor& packed,
@@ -192,4 +201,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("scale"), py::arg("alibi_slopes") = py::none(),
           py::arg("rel_bias") = py::none(), py::arg("bias_zero") = 0,
           py::arg("key_mask") = py::none(), py::arg("causal") = true);
+  // the T5 per-token step (s2s_decode.hip): self-attention with in-place cache
+  // append at a device-side index, and cross-attention under a key mask
+  mod.def("seq2seq_decode_attention", &seq2seq_decode_attention, py::arg("q"), py::arg("k_new"),
+          py::arg("v_new"), py::arg("k_cache"), py::arg("v_cache"), py::arg("cache_idx"),
+          py::arg("rel_bias") = py::none(), py::arg("bias_zero") = 0, py::arg("scale") = 1.0);
+  mod.def("seq2seq_cross_decode_attention", &seq2seq_cross_decode_attention, py::arg("q"),
+          py::arg("k"), py::arg("v"), py::arg("key_mask") = py::none(), py::arg("scale") = 1.0);
 }

@@ -16,6 +16,12 @@ Two GPU paths:
    or TRLX_AMD_NO_GRAPHS=1.
 
 Left-padded prompts are handled with per-row key-start offsets everywhere.
+
+Encoder-decoder (T5) models have the same two paths in ``Seq2SeqDecodeEngine``
+(``Seq2SeqTransformer.generate`` routes to it): the step is
+``decode_step`` over a preallocated ``Seq2SeqDecodeState`` with the decode
+kernels of csrc/s2s_decode.hip, there is no prefill, and the prompt reaches the
+step through the cross-attention K/V buffers and a uint8 key mask.
 """
 
 import os
@@ -417,6 +423,179 @@ class DecodeEngine:
 
 def _graphs_enabled() -> bool:
     return os.environ.get("TRLX_AMD_NO_GRAPHS") != "1"
+
+
+class Seq2SeqDecodeEngine:
+    """``DecodeEngine``'s counterpart for encoder-decoder (T5) models: the
+    per-token step — ``Seq2SeqTransformer.decode_step`` over a preallocated
+    ``Seq2SeqDecodeState``, lm head, optional graph-safe shaping, sampling with
+    the device RNG offset, and the ``decode_advance`` kernel — captured once as
+    a hipGraph and replayed for every token.  There is no prefill: the first
+    replay processes ``decoder_start_token_id`` at cache index 0.  ``run`` with
+    ``use_graph=False`` executes the same step as a plain Python loop over the
+    same state (``TRLX_AMD_NO_GRAPHS=1``, shaping fns that are not graph-safe),
+    so both produce the same tokens bit for bit."""
+
+    def __init__(self, model, batch: int, enc_capacity: int, max_new: int, gen: GenerateConfig,
+                 device, shaping_fn=None):
+        self.model = model
+        self.shaping_fn = shaping_fn  # the one a captured graph contains
+        self.batch = batch
+        self.enc_capacity = enc_capacity
+        self.max_new = max_new
+        self.gen = gen
+        self.device = device
+        self.seed = gen.seed if gen.seed is not None else int(torch.randint(0, 2**31 - 1, (1,)).item())
+        self.state = model.new_decode_state(batch, enc_capacity, max_new, device=device)
+        self.cur_tok = torch.zeros(batch, 1, dtype=torch.long, device=device)
+        self.rng_offset = torch.zeros(1, dtype=torch.long, device=device)
+        self.step_col = torch.zeros(1, dtype=torch.long, device=device)
+        self.finished = torch.zeros(batch, dtype=torch.bool, device=device)
+        # decode_advance also keeps the causal engine's lengths and position
+        # ids; T5 reads neither (the bias index comes from cache_idx)
+        self.seq_lens = torch.zeros(batch, dtype=torch.int32, device=device)
+        self.pos_ids = torch.zeros(batch, dtype=torch.int32, device=device)
+        self.out_tokens = torch.full((batch, max_new), gen.pad_token_id, dtype=torch.long,
+                                     device=device)
+        self.graph = None
+        _ENGINES.add(self)
+
+    def matches(self, batch, enc_len, max_new, gen: GenerateConfig, shaping_fn,
+                use_graph: bool) -> bool:
+        """The plain loop captures nothing, so any shaping fn may share the
+        engine; a graph holds the shaping fn it was captured with.  The seed is
+        a kernel argument, baked into a graph: ``seed=None`` takes whatever
+        the engine has, an explicit seed needs an engine made with it."""
+        return (batch == self.batch and enc_len <= self.enc_capacity
+                and max_new <= self.max_new and gen.sample_key() == self.gen.sample_key()
+                and (gen.seed is None or gen.seed == self.seed)
+                and (not use_graph or shaping_fn is self.shaping_fn))
+
+    def _advance(self, tok):
+        ext = ops._load_ext()
+        eos, pad = self.gen.eos_token_id, self.gen.pad_token_id
+        if ext is not None and tok.is_cuda:
+            ext.decode_advance(tok.contiguous(), self.out_tokens, self.cur_tok.view(-1),
+                               self.finished, self.rng_offset, self.step_col,
+                               self.state.cache_idx, self.seq_lens, self.pos_ids, None, eos, pad)
+            return
+        tok = torch.where(self.finished, torch.full_like(tok, pad), tok)
+        self.finished |= tok == eos
+        self.out_tokens.index_copy_(1, self.step_col, tok.unsqueeze(1))
+        self.cur_tok.copy_(tok.unsqueeze(1))
+        self.rng_offset += 1
+        self.step_col += 1
+        self.state.cache_idx += 1
+
+    def _step(self, shaping_fn):
+        """One token, everything device-side (the graph body)."""
+        h = self.model.decode_step(self.cur_tok, self.state)
+        logits = self.model.project(h)[:, 0]
+        if shaping_fn is not None:
+            logits = shaping_fn(logits.float(), h[:, 0], self.cur_tok[:, 0])
+        if self.gen.do_sample:
+            tok = ops.sample_token(logits, self.gen.temperature, self.gen.top_k, self.gen.top_p,
+                                   seed=self.seed, offset=self.rng_offset)
+        else:
+            tok = logits.argmax(dim=-1)
+        self._advance(tok)
+
+    def _scratch_state(self):
+        """In-bounds dummy state for the warmup and capture runs (they scribble
+        on cache row 0 and the token buffers; ``run`` resets all of it)."""
+        self.state.cache_idx.zero_()
+        self.step_col.zero_()
+        self.rng_offset.zero_()
+        self.finished.zero_()
+        self.cur_tok.fill_(self.model.config.decoder_start_token_id)
+
+    def capture(self):
+        torch.cuda.synchronize()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(2):
+                self._scratch_state()
+                self._step(self.shaping_fn)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        self._scratch_state()
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            self._step(self.shaping_fn)
+
+    def run(self, input_ids, attention_mask, max_new_tokens: int, shaping_fn=None,
+            use_graph: bool = True, reset_rng: bool = False) -> torch.Tensor:
+        """Returns [B, 1 + T_gen]: column 0 is the start token, rows that
+        emitted EOS are padded, and the width is the eager loop's — it stops
+        after the first step at which every row is finished."""
+        enc = self.model.encode(input_ids, attention_mask)
+        rng_before = None
+        if use_graph and self.graph is None:
+            # before begin(): warmup scribbles on the state.  The two warmup
+            # steps and the capture must not consume RNG offsets either.
+            rng_before = self.rng_offset.clone()
+            self.capture()
+        self.state.begin(self.model, enc, attention_mask)
+        start = self.model.config.decoder_start_token_id
+        self.cur_tok.fill_(start)
+        self.step_col.zero_()
+        self.finished.zero_()
+        self.out_tokens.fill_(self.gen.pad_token_id)
+        if reset_rng:
+            # explicit seed: same (seed, inputs) -> same tokens; with no seed
+            # the offset keeps advancing across calls (the seed is baked in)
+            self.rng_offset.zero_()
+        elif rng_before is not None:
+            self.rng_offset.copy_(rng_before)
+
+        done = 0
+        for i in range(max_new_tokens):
+            if use_graph:
+                self.graph.replay()
+            else:
+                self._step(shaping_fn)
+            done = i + 1
+            if done % 16 == 0 and done < max_new_tokens and bool(self.finished.all()):
+                break
+        out = self.out_tokens[:, :done]
+        # the step after which every row had emitted EOS (one host read)
+        is_eos = out == self.gen.eos_token_id
+        first = torch.where(is_eos.any(dim=1), is_eos.int().argmax(dim=1) + 1,
+                            torch.full((self.batch,), done, device=out.device))
+        width = int(first.max())
+        first_col = torch.full((self.batch, 1), start, dtype=torch.long, device=out.device)
+        return torch.cat([first_col, out[:, :width]], dim=1)
+
+
+def seq2seq_generate(model, input_ids, attention_mask=None, max_new_tokens: int = 32,
+                     do_sample: bool = True, temperature: float = 1.0, top_k: int = 0,
+                     top_p: float = 1.0, eos_token_id: int = 1, pad_token_id: int = 0,
+                     seed: Optional[int] = None, shaping_fn: Optional[Callable] = None,
+                     graph_safe_shaping: bool = False) -> torch.Tensor:
+    """The kernel path of ``Seq2SeqTransformer.generate`` (which checks that the
+    model qualifies): finds or builds the model's ``Seq2SeqDecodeEngine`` and
+    runs it, graph-captured unless ``TRLX_AMD_NO_GRAPHS=1`` or the shaping fn
+    is not graph-safe."""
+    if not 0 <= pad_token_id < model.config.vocab_size:
+        # a finished row feeds the pad token back in: the embedding lookup of
+        # an id outside the table would read out of bounds on the device
+        raise ValueError(f"pad_token_id {pad_token_id} lies outside the vocabulary "
+                         f"(0..{model.config.vocab_size - 1})")
+    gen = GenerateConfig(max_new_tokens=max_new_tokens, do_sample=do_sample,
+                         temperature=temperature, top_k=top_k, top_p=top_p,
+                         eos_token_id=eos_token_id, pad_token_id=pad_token_id, seed=seed,
+                         graph_safe_shaping=graph_safe_shaping)
+    use_graph = _graphs_enabled() and (shaping_fn is None or graph_safe_shaping)
+    B, T = input_ids.shape
+    engine = getattr(model, "_decode_engine", None)
+    if (not isinstance(engine, Seq2SeqDecodeEngine)
+            or not engine.matches(B, T, max_new_tokens, gen, shaping_fn, use_graph)):
+        engine = Seq2SeqDecodeEngine(model, B, T, max_new_tokens, gen, input_ids.device,
+                                     shaping_fn=shaping_fn if use_graph else None)
+        model._decode_engine = engine
+    return engine.run(input_ids, attention_mask, max_new_tokens, shaping_fn=shaping_fn,
+                      use_graph=use_graph, reset_rng=seed is not None)
 
 
 @torch.no_grad()

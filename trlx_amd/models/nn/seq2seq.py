@@ -17,11 +17,22 @@ learned bias, so a layer whose bias table requires grad keeps the eager path
 (rocBLAS GEMMs + additive-bias softmax) under grad mode: with
 ``num_layers_unfrozen > 0`` the tables are frozen and every attention
 qualifies; a fully unfrozen T5 trains its self-attention eager (its cross-
-attention and its no_grad passes still qualify).  The per-token generation
-step (``past_kv``) stays eager, and so does everything on CPU.  Dropout is
-not applied to attention probabilities on either path.  Norms, logprob
-gathers and sampling hit the gfx950 kernels.  Decoder generation keeps a KV
-cache and precomputes cross-attention K/V once per prompt.
+attention and its no_grad passes still qualify).  Everything on CPU stays
+eager.  Dropout is not applied to attention probabilities on either path.
+Norms, logprob gathers and sampling hit the gfx950 kernels.
+
+Generation: on the GPU in bf16 at a head dim in
+``ops.SEQ2SEQ_DECODE_HEAD_DIMS`` (64, 128) the per-token step is
+``decode_step`` over a preallocated ``Seq2SeqDecodeState`` — self-attention
+caches appended in place at a device-side index, cross K/V projected once per
+call into static buffers, a uint8 key mask, the decoder's Toeplitz bias vector
+recomputed from the table on every call — through the two decode kernels of
+csrc/s2s_decode.hip, and ``generation.Seq2SeqDecodeEngine`` replays it as one
+hipGraph per token (``TRLX_AMD_NO_GRAPHS=1`` or a shaping fn that is not
+graph-safe: the same kernels in a plain loop).  ``TRLX_AMD_NO_S2S_DECODE=1``,
+other head dims, other dtypes and the CPU keep the eager ``past_kv`` loop
+(``torch.cat`` cache, dense bias, additive masks), which measured 3.6-4.9x
+slower at t5-small size (profiles/t5_decode_notes.md).
 """
 
 from dataclasses import dataclass, field
@@ -358,6 +369,68 @@ class T5Block(nn.Module):
         return x, position_bias, new_self_kv, new_cross_kv
 
 
+class Seq2SeqDecodeState:
+    """Everything ``Seq2SeqTransformer.decode_step`` reads besides the weights,
+    preallocated once and reused by every generate call (and by the captured
+    graph of ``generation.Seq2SeqDecodeEngine``, which bakes the addresses in):
+
+    - ``self_k`` / ``self_v``: per-layer self-attention caches [B, H, S, D],
+      appended in place at ``cache_idx`` (``S`` decoder positions);
+    - ``cross_k`` / ``cross_v``: per-layer cross-attention K/V [B, H, Tcap, D];
+    - ``key_mask``: uint8 [B, Tcap], zero beyond the current prompt, so a
+      shorter prompt reuses the buffers (whatever lies behind the mask is
+      skipped by the kernel, never read);
+    - ``rel_bias`` [H, S] fp32 with ``bias_zero = S - 1``: the decoder's
+      Toeplitz bias vector for one query at any position < S;
+    - ``cache_idx``: int64 [1] on the device, the position of the next token.
+    """
+
+    def __init__(self, model: "Seq2SeqTransformer", batch: int, enc_capacity: int,
+                 max_positions: int, device, dtype):
+        cfg = model.config
+        H, D = cfg.num_heads, cfg.d_kv
+        n = len(model.decoder_blocks)
+        self.batch, self.enc_capacity, self.max_positions = batch, enc_capacity, max_positions
+
+        def buf(length):
+            return [torch.zeros(batch, H, length, D, dtype=dtype, device=device) for _ in range(n)]
+
+        self.self_k, self.self_v = buf(max_positions), buf(max_positions)
+        self.cross_k, self.cross_v = buf(enc_capacity), buf(enc_capacity)
+        self.key_mask = torch.zeros(batch, enc_capacity, dtype=torch.uint8, device=device)
+        self.rel_bias = torch.zeros(H, max_positions, dtype=torch.float32, device=device)
+        self.bias_zero = max_positions - 1
+        self.cache_idx = torch.zeros(1, dtype=torch.long, device=device)
+
+    @torch.no_grad()
+    def begin(self, model: "Seq2SeqTransformer", enc_out: torch.Tensor,
+              attention_mask: Optional[torch.Tensor] = None):
+        """Start a generate call: everything below is written INTO the existing
+        buffers.  The bias vector is recomputed from the table on every call —
+        the table may have been trained since the last one — and so are the
+        cross K/V, from this call's encoder output."""
+        B, T, _ = enc_out.shape
+        assert B == self.batch and T <= self.enc_capacity, (B, T)
+        cfg = model.config
+        H, D = cfg.num_heads, cfg.d_kv
+        owner = model.decoder_blocks[0].self_attn
+        vec, zero = ops.t5_rel_bias(
+            owner.relative_attention_bias.weight, 1, 1, self.max_positions - 1, False,
+            cfg.relative_attention_num_buckets, cfg.relative_attention_max_distance)
+        assert zero == self.bias_zero and vec.shape == self.rel_bias.shape
+        self.rel_bias.copy_(vec)
+        for i, block in enumerate(model.decoder_blocks):
+            ca = block.cross_attn
+            self.cross_k[i][:, :, :T].copy_(ca.k(enc_out).view(B, T, H, D).transpose(1, 2))
+            self.cross_v[i][:, :, :T].copy_(ca.v(enc_out).view(B, T, H, D).transpose(1, 2))
+        self.key_mask.zero_()
+        if attention_mask is None:
+            self.key_mask[:, :T].fill_(1)
+        else:
+            self.key_mask[:, :T].copy_(attention_mask != 0)
+        self.cache_idx.zero_()
+
+
 @dataclass
 class Seq2SeqOutput:
     logits: Optional[torch.Tensor] = None
@@ -441,6 +514,43 @@ class Seq2SeqTransformer(nn.Module):
             new_past.append((self_kv, cross_kv))
         return self.decoder_final_norm(h), new_past, hidden_at
 
+    def new_decode_state(self, batch: int, enc_capacity: int, max_positions: int,
+                         device=None, dtype=None) -> Seq2SeqDecodeState:
+        w = self.shared.weight
+        return Seq2SeqDecodeState(self, batch, enc_capacity, max_positions,
+                                  device if device is not None else w.device,
+                                  dtype if dtype is not None else w.dtype)
+
+    def decode_step(self, cur_tok: torch.Tensor, state: Seq2SeqDecodeState) -> torch.Tensor:
+        """One decoder token over a preallocated ``state`` (after
+        ``state.begin``): ``cur_tok`` [B, 1] is the token at position
+        ``state.cache_idx``.  Per block the two decode-attention ops
+        (``ops.seq2seq_decode_attention`` appends this token's K/V to the self
+        cache in place, ``ops.seq2seq_cross_decode_attention`` reads the
+        prompt's K/V under the key mask): no ``torch.cat``, no dense bias, no
+        additive mask, no host read — the step is the same work for every
+        token, so it can be captured once.  Does NOT advance ``cache_idx``
+        (every layer reads it; the caller bumps it after the step).
+        Returns the final-normed hidden state [B, 1, d_model]."""
+        B = cur_tok.shape[0]
+        H, D = self.config.num_heads, self.config.d_kv
+        h = self.shared(cur_tok.view(B, 1))
+        for i, block in enumerate(self.decoder_blocks):
+            sa = block.self_attn
+            x = block.self_norm(h)
+            a = ops.seq2seq_decode_attention(
+                sa.q(x).view(B, H, D), sa.k(x).view(B, H, D), sa.v(x).view(B, H, D),
+                state.self_k[i], state.self_v[i], state.cache_idx,
+                rel_bias=state.rel_bias, bias_zero=state.bias_zero, scale=1.0)  # T5: unscaled
+            h = h + sa.o(a.view(B, 1, H * D))
+            ca = block.cross_attn
+            q = ca.q(block.cross_norm(h)).view(B, H, 1, D)
+            a = ops.seq2seq_cross_decode_attention(q, state.cross_k[i], state.cross_v[i],
+                                                   key_mask=state.key_mask, scale=1.0)
+            h = h + ca.o(a.view(B, 1, H * D))
+            h = h + block.ffn(block.ffn_norm(h))
+        return self.decoder_final_norm(h)
+
     def decoder_bias(self, q_len: int, device) -> RelBias:
         """The decoder's self-attention position bias for a full pass over
         ``q_len`` tokens, as the hydra and value branches need it to re-enter
@@ -476,12 +586,29 @@ class Seq2SeqTransformer(nn.Module):
                  pad_token_id: Optional[int] = None, seed: Optional[int] = None,
                  shaping_fn=None, **kwargs):
         """Returns decoder token ids [B, 1 + T_gen] starting with
-        decoder_start_token_id (HF seq2seq convention)."""
+        decoder_start_token_id (HF seq2seq convention).
+
+        On the GPU in bf16 at a head dim in ``ops.SEQ2SEQ_DECODE_HEAD_DIMS`` the
+        per-token step is ``decode_step`` inside ``generation.
+        Seq2SeqDecodeEngine``: one hipGraph replay per token, or the same
+        kernels in a plain loop under ``TRLX_AMD_NO_GRAPHS=1`` or with a
+        ``shaping_fn`` not declared ``graph_safe_shaping=True``.  Everything
+        else — CPU, other dtypes or head dims, ``TRLX_AMD_NO_S2S_DECODE=1`` —
+        takes the eager ``past`` loop below."""
         cfg = self.config
         B = input_ids.shape[0]
         device = input_ids.device
         eos = eos_token_id if eos_token_id is not None else cfg.eos_token_id
         pad = pad_token_id if pad_token_id is not None else cfg.pad_token_id
+        if (device.type == "cuda" and self.shared.weight.dtype == torch.bfloat16
+                and ops.seq2seq_decode_enabled(cfg.d_kv) and B > 0 and max_new_tokens > 0):
+            from .generation import seq2seq_generate
+
+            return seq2seq_generate(
+                self, input_ids, attention_mask, max_new_tokens=max_new_tokens,
+                do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p,
+                eos_token_id=eos, pad_token_id=pad, seed=seed, shaping_fn=shaping_fn,
+                graph_safe_shaping=bool(kwargs.get("graph_safe_shaping", False)))
         if seed is None:
             seed = int(torch.randint(0, 2**31 - 1, (1,)).item())
 

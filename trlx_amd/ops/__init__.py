@@ -43,6 +43,10 @@ SEQ2SEQ_FLASH_HEAD_DIMS = (64, 128)
 SEQ2SEQ_FLASH_PREFILL_DEFAULT_DIMS = (64, 128)
 SEQ2SEQ_FLASH_TRAIN_DEFAULT_DIMS = (64, 128)
 
+# The T5 per-token generation step (csrc/s2s_decode.hip; kSeq2SeqDecodeHeadDims
+# in attn_host.h): seq2seq_decode_attention / seq2seq_cross_decode_attention.
+SEQ2SEQ_DECODE_HEAD_DIMS = (64, 128)
+
 
 def _flash_gate(head_dim: int, train: bool, built, prefill_default, train_default) -> bool:
     """The gate behind ``flash_enabled`` / ``seq2seq_flash_enabled``: ``built``
@@ -976,3 +980,46 @@ def seq2seq_attention(q, k, v, rel_bias=None, bias_zero: int = 0, key_mask=None,
         raise RuntimeError("seq2seq_attention: causal training needs Tq == Tk and start_pos == 0")
     return _FlashAttention.apply(q, k, v, None, None, rb, int(bias_zero), km, bool(causal),
                                  int(start_pos), float(scale), ext)
+
+
+def seq2seq_decode_enabled(head_dim: int) -> bool:
+    """Does T5 generation take the cached kernel step at this head dim?
+    ``TRLX_AMD_NO_S2S_DECODE=1`` keeps the eager ``past`` loop (the escape
+    hatch and the A/B baseline of profiles/t5_decode_notes.md)."""
+    return (head_dim in SEQ2SEQ_DECODE_HEAD_DIMS
+            and os.environ.get("TRLX_AMD_NO_S2S_DECODE") != "1")
+
+
+def seq2seq_decode_attention(q, k_new, v_new, k_cache, v_cache, cache_idx, rel_bias=None,
+                             bias_zero: int = 0, scale: float = 1.0):
+    """The T5 self-attention of ONE new token (csrc/s2s_decode.hip): q, k_new,
+    v_new [B, H, D] bf16 are its three projections, ``cache_idx`` a one-element
+    int64 tensor ON THE DEVICE holding its position ``pos``.  Appends k_new /
+    v_new IN PLACE to row ``pos`` of the preallocated caches [B, H, S, D] and
+    attends over keys 0..pos inclusive; ``rel_bias`` [H, L] fp32 with
+    ``bias_zero`` is the Toeplitz bias of ``t5_rel_bias`` (index clamped to
+    [0, L)).  ``pos`` is never read on the host, so a captured graph replays
+    the step for every token; a ``pos`` outside [0, S) writes nothing and
+    returns zeros.  Returns [B, H, 1, D].  On CPU the fp32 reference runs."""
+    B, H, D = k_cache.shape[0], k_cache.shape[1], k_cache.shape[3]
+    q, k_new, v_new = (t.reshape(B, H, D) for t in (q, k_new, v_new))
+    ext = _require_ext("seq2seq_decode_attention") if q.is_cuda else None
+    if ext is None:
+        return reference.seq2seq_decode_attention(q, k_new, v_new, k_cache, v_cache, cache_idx,
+                                                  rel_bias, bias_zero, scale)
+    rb = rel_bias.detach() if rel_bias is not None else None
+    return ext.seq2seq_decode_attention(q.contiguous(), k_new.contiguous(), v_new.contiguous(),
+                                        k_cache, v_cache, cache_idx, rb, int(bias_zero),
+                                        float(scale))
+
+
+def seq2seq_cross_decode_attention(q, k, v, key_mask=None, scale: float = 1.0):
+    """The T5 cross-attention of one new token: q [B, H, 1, D] bf16 against the
+    prompt's k / v [B, H, Tk, D] under ``key_mask`` [B, Tk] uint8 (nonzero =
+    visible, any pattern).  Masked keys are skipped — never loaded — so stale or
+    non-finite rows behind the mask cannot leak; a row with no visible key
+    returns zeros.  Returns [B, H, 1, D].  On CPU the fp32 reference runs."""
+    ext = _require_ext("seq2seq_cross_decode_attention") if q.is_cuda else None
+    if ext is None:
+        return reference.seq2seq_cross_decode_attention(q, k, v, key_mask, scale)
+    return ext.seq2seq_cross_decode_attention(q.contiguous(), k, v, key_mask, float(scale))

@@ -340,3 +340,51 @@ def seq2seq_attention(q, k, v, rel_bias=None, bias_zero: int = 0, key_mask=None,
     scores = scores.masked_fill(~visible, float("-inf"))
     probs = torch.nan_to_num(torch.softmax(scores, dim=-1), nan=0.0)
     return torch.matmul(probs, vv).to(q.dtype)
+
+
+def seq2seq_decode_attention(q, k_new, v_new, k_cache, v_cache, cache_idx, rel_bias=None,
+                             bias_zero: int = 0, scale: float = 1.0):
+    """fp32 reference for the T5 self-attention decode step (csrc/s2s_decode.hip):
+    q / k_new / v_new [B, H, D] are the projections of the one new token at
+    position ``pos = cache_idx[0]``.  Writes k_new / v_new IN PLACE into row
+    ``pos`` of the caches [B, H, S, D], then attends over keys 0..pos inclusive
+    with score ``scale * q.k + rel_bias[h, clamp(key - pos + bias_zero, 0, L-1)]``.
+    A ``pos`` outside [0, S) writes nothing and returns zeros, as the kernel
+    does.  Returns [B, H, 1, D]."""
+    B, H, D = q.shape
+    S = k_cache.shape[2]
+    pos = int(cache_idx.reshape(-1)[0])
+    if not 0 <= pos < S:
+        return torch.zeros(B, H, 1, D, dtype=q.dtype, device=q.device)
+    k_cache[:, :, pos] = k_new.to(k_cache.dtype)
+    v_cache[:, :, pos] = v_new.to(v_cache.dtype)
+    kk = k_cache[:, :, : pos + 1].float()
+    vv = v_cache[:, :, : pos + 1].float()
+    scores = torch.matmul((q.float() * scale).unsqueeze(2), kk.transpose(-1, -2))  # [B,H,1,pos+1]
+    if rel_bias is not None:
+        L = rel_bias.shape[1]
+        idx = (torch.arange(pos + 1, device=q.device) - pos + bias_zero).clamp(0, L - 1)
+        scores = scores + rel_bias.float()[:, idx].view(1, H, 1, pos + 1)
+    probs = torch.softmax(scores, dim=-1)
+    return torch.matmul(probs, vv).to(q.dtype)
+
+
+def seq2seq_cross_decode_attention(q, k, v, key_mask=None, scale: float = 1.0):
+    """fp32 reference for the T5 cross-attention decode step: q [B, H, 1, D]
+    against k / v [B, H, Tk, D]; key j of row b is visible iff
+    ``key_mask[b, j] != 0`` (any mask).  Masked keys are skipped, not weighted
+    by zero: non-finite K/V rows behind the mask do not reach the output.  A
+    row with no visible key returns zeros."""
+    B, H, _, D = q.shape
+    Tk = k.shape[2]
+    kk, vv = k.float(), v.float()
+    visible = torch.ones(B, 1, 1, Tk, dtype=torch.bool, device=q.device)
+    if key_mask is not None:
+        visible = (key_mask.to(q.device) != 0).view(B, 1, 1, Tk)
+        keep = visible.view(B, 1, Tk, 1)
+        kk = torch.where(keep, kk, torch.zeros_like(kk))
+        vv = torch.where(keep, vv, torch.zeros_like(vv))
+    scores = torch.matmul(q.float() * scale, kk.transpose(-1, -2))
+    scores = scores.masked_fill(~visible, float("-inf"))
+    probs = torch.nan_to_num(torch.softmax(scores, dim=-1), nan=0.0)
+    return torch.matmul(probs, vv).to(q.dtype)
