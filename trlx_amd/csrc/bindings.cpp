@@ -59,6 +59,12 @@ std::vector<at::Tensor> lm_logprobs_v2_with_lse(const at::Tensor& hidden,
                                                 const at::Tensor& labels, bool want_lse);
 at::Tensor ce_dlogits(const at::Tensor& hidden, const at::Tensor& weight,
                       const at::Tensor& labels, const at::Tensor& lse, const at::Tensor& dlp);
+std::vector<at::Tensor> linear_gather_lse_fwd(const at::Tensor& x, const at::Tensor& w,
+                                              const at::Tensor& bias, const at::Tensor& idx);
+at::Tensor linear_gather_lse_bwd(const at::Tensor& x, const at::Tensor& w,
+                                 const at::Tensor& bias, const at::Tensor& idx,
+                                 const at::Tensor& lse, const at::Tensor& g_val,
+                                 const at::Tensor& g_lse);
 at::Tensor fused_decode_attention(const at::Tensor& qkv, at::Tensor& kcache, at::Tensor& vcache,
                                   const at::Tensor& seq_lens,
                                   const c10::optional<at::Tensor>& seq_starts,
@@ -171,6 +177,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("skinny_gemm_fp8", &skinny_gemm_fp8);
   mod.def("lm_logprobs_v2_with_lse", &lm_logprobs_v2_with_lse);
   mod.def("ce_dlogits", &ce_dlogits);
+  mod.def("linear_gather_lse_fwd", &linear_gather_lse_fwd);
+  mod.def("linear_gather_lse_bwd", &linear_gather_lse_bwd);
   mod.def("decode_advance", &decode_advance);
   mod.def("fused_decode_attention", &fused_decode_attention, py::arg("qkv"),
           py::arg("k_cache"), py::arg("v_cache"), py::arg("seq_lens"), py::arg("seq_starts"),

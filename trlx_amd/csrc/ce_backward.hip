@@ -49,16 +49,27 @@ __device__ __forceinline__ void stage_half(const bf16_t* __restrict__ src, int s
   }
 }
 
+// GATHER_LSE: the backward of linear_gather_lse (the ILQL Q heads), whose two
+// outputs carry independent upstream gradients:
+//   z = x @ w^T + bias,  dz[n,v] = g_lse[n] * exp(z[n,v] - lse[n])
+//                                 + g_val[n] * 1{v == idx[n]}
+// `dlp` is then g_val and `g_lse` the second per-row coefficient, staged next
+// to it in row_s; the bias joins acc in the epilogue (a lane's four columns
+// are fixed, so four loads).  Off, bias and g_lse are never read and this is
+// the CE backward above — the g_val = g, g_lse = -g case in one coefficient.
+template <bool GATHER_LSE>
 __global__ __launch_bounds__(BLOCK3) void ce_dlogits_kernel(
     const bf16_t* __restrict__ hidden, const bf16_t* __restrict__ weight,
     const long* __restrict__ labels, const float* __restrict__ lse,
     const float* __restrict__ dlp, bf16_t* __restrict__ dlogits, int N, int H, int V, int nV,
-    int nM) {
+    int nM, const float* __restrict__ bias, const float* __restrict__ g_lse) {
+  // (the GATHER_LSE arguments come last, so the others keep their slots)
+  constexpr int RS = GATHER_LSE ? 3 : 2;  // row_s floats per row
   extern __shared__ char smem[];
   char* a_base = smem;
   char* b_base = smem + 2 * TILE_B;
   long* lab_s = reinterpret_cast<long*>(smem + 4 * TILE_B);           // [256]
-  float* row_s = reinterpret_cast<float*>(smem + 4 * TILE_B + 2048);  // [256][2]: lse, dlp
+  float* row_s = reinterpret_cast<float*>(smem + 4 * TILE_B + 2048);  // [256][RS]: lse, dlp(, g_lse)
 
   const int nwg = nV * nM;
   int wg = blockIdx.y * gridDim.x + blockIdx.x;
@@ -81,8 +92,9 @@ __global__ __launch_bounds__(BLOCK3) void ce_dlogits_kernel(
   for (int i = tid; i < BM3; i += BLOCK3) {
     const int n = row0 + i;
     lab_s[i] = (n < N) ? labels[n] : -1;
-    row_s[i * 2] = (n < N) ? lse[n] : 0.f;
-    row_s[i * 2 + 1] = (n < N) ? dlp[n] : 0.f;
+    row_s[i * RS] = (n < N) ? lse[n] : 0.f;
+    row_s[i * RS + 1] = (n < N) ? dlp[n] : 0.f;
+    if constexpr (GATHER_LSE) row_s[i * RS + 2] = (n < N) ? g_lse[n] : 0.f;
   }
 
   f32x4_ce acc[8][4];
@@ -149,6 +161,11 @@ __global__ __launch_bounds__(BLOCK3) void ce_dlogits_kernel(
   // epilogue: dlogits = dlp * (1{label} - exp(logit - lse)), straight from acc
   const int cgrp = lane >> 4;
   const int ccol0 = wave_n * 64 + (lane & 15);
+  float bj[4] = {0.f, 0.f, 0.f, 0.f};
+  if constexpr (GATHER_LSE) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) bj[j] = bias[min(col0 + ccol0 + j * 16, max_br)];
+  }
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
 #pragma unroll
@@ -156,15 +173,23 @@ __global__ __launch_bounds__(BLOCK3) void ce_dlogits_kernel(
       const int trow = wave_m * 128 + i * 16 + cgrp * 4 + r;
       const int n = row0 + trow;
       if (n >= N) continue;
-      const float l = row_s[trow * 2];
-      const float g = row_s[trow * 2 + 1];
+      const float l = row_s[trow * RS];
+      const float g = row_s[trow * RS + 1];
+      float gl = 0.f;
+      if constexpr (GATHER_LSE) gl = row_s[trow * RS + 2];
       const long lab = lab_s[trow];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int v = col0 + ccol0 + j * 16;
         if (v >= V) continue;
-        float p = __expf(acc[i][j][r] - l);
-        float d = g * ((v == lab ? 1.f : 0.f) - p);
+        float d;
+        if constexpr (GATHER_LSE) {
+          float p = __expf(acc[i][j][r] + bj[j] - l);
+          d = gl * p + (v == lab ? g : 0.f);
+        } else {
+          float p = __expf(acc[i][j][r] - l);
+          d = g * ((v == lab ? 1.f : 0.f) - p);
+        }
         ScalarIO<bf16_t>::store(dlogits + (size_t)n * V + v, d);
       }
     }
@@ -172,11 +197,12 @@ __global__ __launch_bounds__(BLOCK3) void ce_dlogits_kernel(
 }
 
 constexpr int CE_LDS = 4 * TILE_B + 2048 + BM3 * 2 * (int)sizeof(float);
+constexpr int GL_LDS = 4 * TILE_B + 2048 + BM3 * 3 * (int)sizeof(float);  // GATHER_LSE
 
-}  // namespace
-
-at::Tensor ce_dlogits(const at::Tensor& hidden, const at::Tensor& weight,
-                      const at::Tensor& labels, const at::Tensor& lse, const at::Tensor& dlp) {
+// bias == nullptr: the CE backward; otherwise the gather+lse backward
+at::Tensor launch_dlogits(const at::Tensor& hidden, const at::Tensor& weight, const float* bias,
+                          const at::Tensor& labels, const at::Tensor& lse,
+                          const at::Tensor& dlp, const float* g_lse) {
   TORCH_CHECK(hidden.is_cuda() && hidden.dtype() == at::kBFloat16 && hidden.dim() == 2 &&
               hidden.is_contiguous());
   TORCH_CHECK(weight.dtype() == at::kBFloat16 && weight.is_contiguous());
@@ -193,16 +219,40 @@ at::Tensor ce_dlogits(const at::Tensor& hidden, const at::Tensor& weight,
   auto stream = c10::hip::getCurrentHIPStream();
   static bool configured = false;
   if (!configured) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ce_dlogits_kernel),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ce_dlogits_kernel<false>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, CE_LDS);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ce_dlogits_kernel<true>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, GL_LDS);
     configured = true;
   }
   dim3 grid(nV, nM);
-  ce_dlogits_kernel<<<grid, BLOCK3, CE_LDS, stream>>>(
+  auto* kern = bias ? &ce_dlogits_kernel<true> : &ce_dlogits_kernel<false>;
+  kern<<<grid, BLOCK3, bias ? GL_LDS : CE_LDS, stream>>>(
       reinterpret_cast<const bf16_t*>(hidden.data_ptr()),
       reinterpret_cast<const bf16_t*>(weight.data_ptr()), labels.data_ptr<long>(),
       lse.data_ptr<float>(), dlp.contiguous().data_ptr<float>(),
-      reinterpret_cast<bf16_t*>(dlogits.data_ptr()), N, H, V, nV, nM);
+      reinterpret_cast<bf16_t*>(dlogits.data_ptr()), N, H, V, nV, nM, bias, g_lse);
   HIP_CHECK_LAST();
   return dlogits;
+}
+
+}  // namespace
+
+at::Tensor ce_dlogits(const at::Tensor& hidden, const at::Tensor& weight,
+                      const at::Tensor& labels, const at::Tensor& lse, const at::Tensor& dlp) {
+  return launch_dlogits(hidden, weight, nullptr, labels, lse, dlp, nullptr);
+}
+
+at::Tensor linear_gather_lse_bwd(const at::Tensor& x, const at::Tensor& w,
+                                 const at::Tensor& bias, const at::Tensor& idx,
+                                 const at::Tensor& lse, const at::Tensor& g_val,
+                                 const at::Tensor& g_lse) {
+  TORCH_CHECK(bias.is_cuda() && bias.dtype() == at::kFloat && bias.is_contiguous() &&
+              bias.numel() == w.size(0));
+  TORCH_CHECK(idx.dtype() == at::kLong && idx.is_contiguous());
+  TORCH_CHECK(lse.dtype() == at::kFloat && lse.is_contiguous());
+  TORCH_CHECK(g_val.dtype() == at::kFloat && g_lse.dtype() == at::kFloat &&
+              g_lse.numel() == x.size(0));
+  auto gl = g_lse.contiguous();
+  return launch_dlogits(x, w, bias.data_ptr<float>(), idx, lse, g_val, gl.data_ptr<float>());
 }

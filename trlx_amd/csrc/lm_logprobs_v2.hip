@@ -102,12 +102,20 @@ struct MSv2 {
 // mode: perf-probe ablation bits (0 = normal). 1: skip epilogue, 2: skip
 // ds_reads, 4: skip MFMAs — numerically invalid, used to bisect where the
 // kernel's time goes on real hardware.
-template <bool NOWAIT>
+//
+// BIAS: z = x @ w^T + bias[v] (the ILQL Q heads, linear_gather_lse_fwd).  The
+// bias joins the accumulators on their way into the LDS C tile — a lane's
+// four columns (one per j) are the same for every i and r, so it loads four
+// floats once — and the row scan and the label gather then see z.  With
+// BIAS off the pointer is never read and the kernel is the lm_head one.
+template <bool NOWAIT, bool BIAS>
 __global__ __launch_bounds__(BLOCK2) void lm_logprobs_v2_kernel(
     const bf16_t* __restrict__ hidden, const bf16_t* __restrict__ weight,
     float* __restrict__ partials,  // [nV][N][2]
     float* __restrict__ label_logit, const long* __restrict__ labels, int N, int H, int V,
-    int nV, int nM, int mode) {
+    int nV, int nM, int mode,
+    const float* __restrict__ bias) {  // [V], BIAS only; last, so the
+                                       // other arguments keep their slots
   extern __shared__ char smem[];
   // K-loop:   [ A buf0 | A buf1 | B buf0 | B buf1 | ... | labels 2K ]
   // epilogue: [ c_lds fp32 [128][260] | cpart [128][4][2] | labels 2K ]
@@ -246,6 +254,12 @@ __global__ __launch_bounds__(BLOCK2) void lm_logprobs_v2_kernel(
                                         // row-per-lane reads walk all banks
   const int row_in_half = tid & 127;    // one row per lane across 2 waves-of-rows
   const int qc0 = (tid >> 7) * 64;      // this thread's column span
+  float bj[4] = {0.f, 0.f, 0.f, 0.f};   // this lane's four C columns' bias
+  if constexpr (BIAS) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      bj[j] = bias[min(col0 + wave_n * 64 + j * 16 + (lane & 15), max_brow)];
+  }
 #pragma unroll
   for (int half = 0; half < 2; ++half) {
     __builtin_amdgcn_s_barrier();
@@ -258,7 +272,10 @@ __global__ __launch_bounds__(BLOCK2) void lm_logprobs_v2_kernel(
           for (int r = 0; r < 4; ++r) {
             const int rr = i * 16 + (lane >> 4) * 4 + r;
             const int cc = wave_n * 64 + j * 16 + (lane & 15);
-            c_lds[rr * CPAD + cc] = acc[i][j][r];
+            if constexpr (BIAS)
+              c_lds[rr * CPAD + cc] = acc[i][j][r] + bj[j];
+            else
+              c_lds[rr * CPAD + cc] = acc[i][j][r];
           }
     }
     __builtin_amdgcn_s_barrier();
@@ -314,6 +331,9 @@ __global__ __launch_bounds__(BLOCK2) void lm_logprobs_v2_kernel(
   }
 }
 
+// SPLIT: the label value already sits in its own output (label_logit), so
+// only the logsumexp is written — the two outputs of linear_gather_lse_fwd.
+template <bool SPLIT>
 __global__ void lm_logprobs_v2_reduce(const float* __restrict__ partials,
                                       const float* __restrict__ label_logit,
                                       float* __restrict__ out, float* __restrict__ lse_out,
@@ -347,8 +367,12 @@ __global__ void lm_logprobs_v2_reduce(const float* __restrict__ partials,
   }
   if (lane == 0) {
     const float lse = ms.m + logf(ms.s);
-    out[n] = label_logit[n] - lse;
-    if (lse_out) lse_out[n] = lse;
+    if constexpr (SPLIT) {
+      lse_out[n] = lse;
+    } else {
+      out[n] = label_logit[n] - lse;
+      if (lse_out) lse_out[n] = lse;
+    }
   }
 }
 
@@ -365,9 +389,12 @@ at::Tensor lm_logprobs_v2(const at::Tensor& hidden, const at::Tensor& weight,
   return lm_logprobs_v2_with_lse(hidden, weight, labels, false)[0];
 }
 
-std::vector<at::Tensor> lm_logprobs_v2_with_lse(const at::Tensor& hidden,
-                                                const at::Tensor& weight,
-                                                const at::Tensor& labels, bool want_lse) {
+namespace {
+
+// One host path for both entry points: bias == nullptr is the lm_head op
+// (out = label logit - lse), otherwise out = z at the label and lse apart.
+std::vector<at::Tensor> launch_v2(const at::Tensor& hidden, const at::Tensor& weight,
+                                  const float* bias, const at::Tensor& labels, bool want_lse) {
   const int mode = [] {
     const char* e = getenv("TRLX_AMD_LMLP_MODE");
     return e ? atoi(e) : 0;
@@ -381,14 +408,17 @@ std::vector<at::Tensor> lm_logprobs_v2_with_lse(const at::Tensor& hidden,
   const int V = weight.size(0);
   TORCH_CHECK(weight.size(1) == H && labels.numel() == N);
   TORCH_CHECK(H % BK2 == 0, "lm_logprobs_v2: hidden size must be a multiple of 64");
-  auto out = at::empty({N}, hidden.options().dtype(at::kFloat));
-  auto lse = want_lse ? at::empty({N}, hidden.options().dtype(at::kFloat))
-                      : at::empty({0}, hidden.options().dtype(at::kFloat));
+  const bool split = bias != nullptr;
+  auto fopt = hidden.options().dtype(at::kFloat);
+  // split: the main kernel writes the label value straight into `out`
+  // (zero where no tile owns the label, as label_logit below)
+  auto out = split ? at::zeros({N}, fopt) : at::empty({N}, fopt);
+  auto lse = want_lse ? at::empty({N}, fopt) : at::empty({0}, fopt);
   if (N == 0) return {out, lse};
   const int nV = (V + BN2 - 1) / BN2;
   const int nM = (N + BM2 - 1) / BM2;
-  auto partials = at::empty({nV, (long)N, 2}, hidden.options().dtype(at::kFloat));
-  auto label_logit = at::zeros({N}, hidden.options().dtype(at::kFloat));
+  auto partials = at::empty({nV, (long)N, 2}, fopt);
+  auto label_logit = split ? out : at::zeros({N}, fopt);
   auto stream = c10::hip::getCurrentHIPStream();
   const bool nowait = [] {
     const char* e = getenv("TRLX_AMD_LMLP_NOWAIT");
@@ -396,27 +426,50 @@ std::vector<at::Tensor> lm_logprobs_v2_with_lse(const at::Tensor& hidden,
   }();
   static bool lds_configured = false;
   if (!lds_configured) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&lm_logprobs_v2_kernel<false>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, V2_LDS);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&lm_logprobs_v2_kernel<true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, V2_LDS);
+    (void)hipFuncSetAttribute(
+        reinterpret_cast<const void*>(&lm_logprobs_v2_kernel<false, false>),
+        hipFuncAttributeMaxDynamicSharedMemorySize, V2_LDS);
+    (void)hipFuncSetAttribute(
+        reinterpret_cast<const void*>(&lm_logprobs_v2_kernel<true, false>),
+        hipFuncAttributeMaxDynamicSharedMemorySize, V2_LDS);
+    (void)hipFuncSetAttribute(
+        reinterpret_cast<const void*>(&lm_logprobs_v2_kernel<false, true>),
+        hipFuncAttributeMaxDynamicSharedMemorySize, V2_LDS);
     lds_configured = true;
   }
   dim3 grid(nV, nM);
-  if (nowait)
-    lm_logprobs_v2_kernel<true><<<grid, BLOCK2, V2_LDS, stream>>>(
-        reinterpret_cast<const bf16_t*>(hidden.data_ptr()),
-        reinterpret_cast<const bf16_t*>(weight.data_ptr()), partials.data_ptr<float>(),
-        label_logit.data_ptr<float>(), labels.data_ptr<long>(), N, H, V, nV, nM, mode);
-  else
-    lm_logprobs_v2_kernel<false><<<grid, BLOCK2, V2_LDS, stream>>>(
-        reinterpret_cast<const bf16_t*>(hidden.data_ptr()),
-        reinterpret_cast<const bf16_t*>(weight.data_ptr()), partials.data_ptr<float>(),
-        label_logit.data_ptr<float>(), labels.data_ptr<long>(), N, H, V, nV, nM, mode);
+  auto* kern = split ? &lm_logprobs_v2_kernel<false, true>
+                     : nowait ? &lm_logprobs_v2_kernel<true, false>
+                              : &lm_logprobs_v2_kernel<false, false>;
+  kern<<<grid, BLOCK2, V2_LDS, stream>>>(
+      reinterpret_cast<const bf16_t*>(hidden.data_ptr()),
+      reinterpret_cast<const bf16_t*>(weight.data_ptr()), partials.data_ptr<float>(),
+      label_logit.data_ptr<float>(), labels.data_ptr<long>(), N, H, V, nV, nM, mode, bias);
   const int wpb = 256 / WAVE;
-  lm_logprobs_v2_reduce<<<(N + wpb - 1) / wpb, 256, 0, stream>>>(
-      partials.data_ptr<float>(), label_logit.data_ptr<float>(), out.data_ptr<float>(),
-      want_lse ? lse.data_ptr<float>() : nullptr, N, nV);
+  if (split)
+    lm_logprobs_v2_reduce<true><<<(N + wpb - 1) / wpb, 256, 0, stream>>>(
+        partials.data_ptr<float>(), nullptr, nullptr, lse.data_ptr<float>(), N, nV);
+  else
+    lm_logprobs_v2_reduce<false><<<(N + wpb - 1) / wpb, 256, 0, stream>>>(
+        partials.data_ptr<float>(), label_logit.data_ptr<float>(), out.data_ptr<float>(),
+        want_lse ? lse.data_ptr<float>() : nullptr, N, nV);
   HIP_CHECK_LAST();
   return {out, lse};
+}
+
+}  // namespace
+
+std::vector<at::Tensor> lm_logprobs_v2_with_lse(const at::Tensor& hidden,
+                                                const at::Tensor& weight,
+                                                const at::Tensor& labels, bool want_lse) {
+  return launch_v2(hidden, weight, nullptr, labels, want_lse);
+}
+
+// (val, lse) of z = x @ w^T + bias: val[n] = z[n, idx[n]], lse[n] =
+// logsumexp_v z[n, v].  idx outside [0, V) gives val 0.
+std::vector<at::Tensor> linear_gather_lse_fwd(const at::Tensor& x, const at::Tensor& w,
+                                              const at::Tensor& bias, const at::Tensor& idx) {
+  TORCH_CHECK(bias.is_cuda() && bias.dtype() == at::kFloat && bias.is_contiguous() &&
+              bias.numel() == w.size(0));
+  return launch_v2(x, w, bias.data_ptr<float>(), idx, true);
 }

@@ -21,6 +21,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .. import ops
 from ..data.ilql_types import ILQLBatch
 from ..data.method_configs import MethodConfig, register_method
 from ..utils.modeling import flatten_dict, get_tensor_stats, make_head
@@ -51,6 +52,32 @@ def batched_index_select(x: torch.Tensor, idxs: torch.Tensor, dim: int = 1) -> t
     return x.gather(dim=dim, index=idxs)
 
 
+def ilql_actions(labels) -> torch.Tensor:
+    """The taken action (next token) of every action slot of a batch, [B, na]."""
+    if isinstance(labels, ILQLBatch):
+        return labels.input_ids[:, 1:].gather(dim=1, index=labels.actions_ixs)
+    return labels.decoder_input_ids[:, 1:]
+
+
+@dataclass
+class ILQLActionValues:
+    """What the ILQL loss reads from the heads, already reduced to the taken
+    actions (``ILQLHeads.forward_actions``): no [B, na, V] tensor behind it.
+
+    :param q: per Q head, Q(s, a) at the taken action, [B, na]
+    :param q_lse: per Q head, logsumexp over the vocabulary of Q(s, .), [B, na]
+    :param target_q: per target head, target Q(s, a), [B, na], detached
+    :param vs: V(s), [B, ns, 1]
+    :param action_logprobs: log pi(a | s) of the language model, [B, na]
+    """
+
+    q: Tuple[torch.Tensor, ...]
+    q_lse: Tuple[torch.Tensor, ...]
+    target_q: Tuple[torch.Tensor, ...]
+    vs: torch.Tensor
+    action_logprobs: torch.Tensor
+
+
 @dataclass
 @register_method
 class ILQLConfig(MethodConfig):
@@ -79,21 +106,40 @@ class ILQLConfig(MethodConfig):
 
     def loss(self, outputs, labels: ILQLBatch):
         """The ILQL objective: TD-Q + expectile-V + CQL + AWAC
-        (semantics of reference modeling_ilql.py:94-166)."""
-        logits, (qs, target_qs, vs) = outputs
-        terminal_mask = labels.dones[:, :-1]
-        n_nonterminal = terminal_mask.sum().clamp(min=1)  # device tensor: no
-        # host sync in the hot loop, and safe under hipGraph capture
+        (semantics of reference modeling_ilql.py:94-166).
 
-        if isinstance(labels, ILQLBatch):
-            actions = labels.input_ids[:, 1:].gather(dim=1, index=labels.actions_ixs).unsqueeze(-1)
-        else:
-            actions = labels.decoder_input_ids[:, 1:].unsqueeze(-1)
+        ``outputs`` is ``(logits, (qs, target_qs, vs))`` with vocabulary-wide
+        heads, or an ``ILQLActionValues`` already reduced to the taken
+        actions; both feed the same objective (``_loss_from_action_terms``)."""
+        if isinstance(outputs, ILQLActionValues):
+            return self._loss_from_action_terms(
+                list(outputs.q), [t.detach() for t in outputs.target_q], outputs.vs,
+                [lse - q for lse, q in zip(outputs.q_lse, outputs.q)],
+                -outputs.action_logprobs, labels)
+        logits, (qs, target_qs, vs) = outputs
+        actions = ilql_actions(labels).unsqueeze(-1)
         nactions = actions.shape[1]
         bsize, _, dsize = logits.shape
 
         Q = [q.gather(-1, actions).squeeze(-1) for q in qs]
         targetQs = [q.gather(-1, actions).squeeze(-1).detach() for q in target_qs]
+        cql_ce = [
+            F.cross_entropy(q.reshape(-1, dsize), actions.reshape(-1), reduction="none")
+            .reshape(bsize, nactions) for q in qs
+        ]
+        action_logits = batched_index_select(logits, labels.actions_ixs, dim=1)
+        awac_ce = F.cross_entropy(
+            action_logits.reshape(-1, dsize).float(), actions.reshape(-1), reduction="none"
+        ).reshape(bsize, nactions)
+        return self._loss_from_action_terms(Q, targetQs, vs, cql_ce, awac_ce, labels)
+
+    def _loss_from_action_terms(self, Q, targetQs, vs, cql_ce, awac_ce, labels):
+        """The objective after the gathers.  Per taken action: ``Q`` and
+        ``targetQs`` (lists of [B, na]), ``cql_ce`` = logsumexp Q(s, .) -
+        Q(s, a) per Q head, ``awac_ce`` = -log pi(a | s)."""
+        terminal_mask = labels.dones[:, :-1]
+        n_nonterminal = terminal_mask.sum().clamp(min=1)  # device tensor: no
+        # host sync in the hot loop, and safe under hipGraph capture
         targetQ = reduce(torch.minimum, targetQs)
 
         # len(states) == len(rewards) + 1: V of current states / next states
@@ -107,19 +153,11 @@ class ILQLConfig(MethodConfig):
         expectile_w = torch.where(targetQ >= V, self.tau, 1 - self.tau)
         loss_v = (expectile_w * (targetQ - V).pow(2) * terminal_mask).sum() / n_nonterminal
 
-        def cql_loss(q):
-            ce = F.cross_entropy(q.reshape(-1, dsize), actions.reshape(-1), reduction="none")
-            return (ce.reshape(bsize, nactions) * terminal_mask).sum() / n_nonterminal
+        loss_cql = sum((ce * terminal_mask).sum() / n_nonterminal for ce in cql_ce)
 
-        loss_cql = sum(cql_loss(q) for q in qs)
-
-        action_logits = batched_index_select(logits, labels.actions_ixs, dim=1)
-        cross_entropy = F.cross_entropy(
-            action_logits.reshape(-1, dsize).float(), actions.reshape(-1), reduction="none"
-        ).reshape(bsize, nactions)
         with torch.no_grad():
             awac_weight = torch.exp(self.beta * (targetQ - V))
-        loss_awac = torch.sum(cross_entropy * awac_weight * terminal_mask) / n_nonterminal
+        loss_awac = torch.sum(awac_ce * awac_weight * terminal_mask) / n_nonterminal
 
         loss = loss_q + loss_v + self.cql_scale * loss_cql + self.awac_scale * loss_awac
 
@@ -170,6 +208,32 @@ class ILQLHeads(nn.Module):
         vs = self.v_head(states_hs)
         return qs, target_qs, vs
 
+    def forward_actions(self, hs: torch.Tensor, states_ixs: torch.Tensor,
+                        actions_ixs: torch.Tensor, actions: torch.Tensor):
+        """The heads reduced to the taken ``actions`` [B, na]: per Q head
+        ``(Q(s, a), logsumexp_v Q(s, v))`` through ``ops.linear_gather_lse``
+        (no [N, V] forward tensor), per target head Q(s, a) from the gathered
+        weight rows (no vocabulary-wide GEMM), and V as in ``forward``.
+        Returns ``(q, q_lse, target_q, vs)``."""
+        hs = hs.to(self.v_head[0].weight.dtype)
+        states_hs = batched_index_select(hs, states_ixs, 1)
+        actions_hs = batched_index_select(hs, actions_ixs, 1)
+        flat_hs = actions_hs.reshape(-1, actions_hs.shape[-1])
+        idx = actions.reshape(-1)
+        q, q_lse = [], []
+        for head in self.q_heads:
+            val, lse = ops.linear_gather_lse(head[1](head[0](flat_hs)), head[2].weight,
+                                             head[2].bias, idx)
+            q.append(val.reshape(actions.shape))
+            q_lse.append(lse.reshape(actions.shape))
+        with torch.no_grad():
+            target_q = tuple(
+                ops.gathered_linear(head[1](head[0](flat_hs)), head[2].weight, head[2].bias,
+                                    idx).reshape(actions.shape)
+                for head in self.target_q_heads)
+        vs = self.v_head(states_hs)
+        return tuple(q), tuple(q_lse), target_q, vs
+
     def sync_target_q_heads(self):
         """Polyak update: target <- alpha*q + (1-alpha)*target."""
         with torch.no_grad():
@@ -185,6 +249,7 @@ class CausalILQLOutput:
     target_qs: Optional[Tuple[torch.Tensor, ...]] = None
     vs: Optional[torch.Tensor] = None
     last_hidden_state: Optional[torch.Tensor] = None
+    action_values: Optional[ILQLActionValues] = None
 
 
 class AutoModelForCausalLMWithILQLHeads(PreTrainedModelWrapper):
@@ -203,7 +268,23 @@ class AutoModelForCausalLMWithILQLHeads(PreTrainedModelWrapper):
         self.ilql_heads = ILQLHeads(self.config.hidden_size, self.config.vocab_size, two_qs, alpha)
 
     def forward(self, input_ids, attention_mask=None, position_ids=None,
-                actions_ixs=None, states_ixs=None, **kwargs):
+                actions_ixs=None, states_ixs=None, fused_actions=None, **kwargs):
+        """``fused_actions`` [B, na] (the taken actions, ``ilql_actions``):
+        return only ``action_values`` — neither logits nor vocabulary-wide
+        Q tensors are built.  An lm_head with a bias keeps the full path."""
+        if fused_actions is not None and self.base_model.lm_head.bias is None:
+            out = self.base_model(input_ids, attention_mask=attention_mask,
+                                  position_ids=position_ids, return_logits=False)
+            hs = out.last_hidden_state
+            q, q_lse, target_q, vs = self.ilql_heads.forward_actions(
+                hs, states_ixs, actions_ixs, fused_actions)
+            actions_hs = batched_index_select(hs, actions_ixs, 1)
+            action_logprobs = ops.lm_logprobs_train(
+                actions_hs.reshape(-1, hs.shape[-1]), self.base_model.lm_head.weight,
+                fused_actions.reshape(-1)).reshape(fused_actions.shape)
+            return CausalILQLOutput(
+                vs=vs, last_hidden_state=hs,
+                action_values=ILQLActionValues(q, q_lse, target_q, vs, action_logprobs))
         out = self.base_model(input_ids, attention_mask=attention_mask, position_ids=position_ids)
         qs, target_qs, vs = self.ilql_heads(out.last_hidden_state, states_ixs=states_ixs,
                                             actions_ixs=actions_ixs)

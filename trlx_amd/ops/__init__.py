@@ -225,6 +225,64 @@ def lm_logprobs_train(hidden: torch.Tensor, weight: torch.Tensor,
     return logprobs_of_labels(logits, labels)
 
 
+class _LinearGatherLSE(torch.autograd.Function):
+    """z = x @ w^T + bias reduced to (z at idx, logsumexp z) per row without
+    an [N, V] forward tensor (csrc/lm_logprobs_v2.hip, BIAS instantiation);
+    the backward recomputes z tile-by-tile into the bf16 dz
+    (csrc/ce_backward.hip, GATHER_LSE instantiation) and contracts it on
+    hipBLASLt, as _LMLogprobsTrain does."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, idx, ext):
+        xb = x.to(torch.bfloat16).contiguous()
+        wb = weight.to(torch.bfloat16).contiguous()
+        b = bias.float().contiguous()
+        val, lse = ext.linear_gather_lse_fwd(xb, wb, b, idx)
+        ctx.save_for_backward(xb, wb, b, idx, lse)
+        ctx.in_dtypes = (x.dtype, weight.dtype, bias.dtype)
+        return val, lse
+
+    @staticmethod
+    def backward(ctx, g_val, g_lse):
+        xb, wb, b, idx, lse = ctx.saved_tensors
+        ext = _require_ext("linear_gather_lse")
+        dz = ext.linear_gather_lse_bwd(xb, wb, b, idx, lse, g_val.float().contiguous(),
+                                       g_lse.float().contiguous())
+        need = ctx.needs_input_grad
+        dx = (dz @ wb).to(ctx.in_dtypes[0]) if need[0] else None
+        dw = (dz.t() @ xb).to(ctx.in_dtypes[1]) if need[1] else None
+        # fp32 accumulation of the bf16 dz without an [N, V] fp32 copy
+        db = dz.sum(0, dtype=torch.float32).to(ctx.in_dtypes[2]) if need[2] else None
+        return dx, dw, db, None, None
+
+
+def linear_gather_lse(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor,
+                      idx: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``z = x @ weight^T + bias`` reduced per row to ``(z[n, idx[n]],
+    logsumexp_v z[n, v])``, both differentiable.  x [N,K], weight [V,K],
+    bias [V], idx [N] int64 -> two [N] tensors.
+
+    GPU with K % 64 == 0: the fused kernels on bf16-rounded x and weight (fp32
+    bias, fp32 accumulation and outputs); the only [N, V] tensor is the bf16
+    dz of the backward.  Otherwise: F.linear + gather + logsumexp in the input
+    dtype."""
+    if x.is_cuda and x.shape[-1] % 64 == 0:
+        ext = _require_ext("linear_gather_lse")
+        if ext is not None and hasattr(ext, "linear_gather_lse_fwd"):
+            return _LinearGatherLSE.apply(x, weight, bias, idx.contiguous(), ext)
+    z = torch.nn.functional.linear(x, weight, bias)
+    return z.gather(-1, idx.unsqueeze(-1)).squeeze(-1), torch.logsumexp(z, dim=-1)
+
+
+def gathered_linear(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor,
+                    idx: torch.Tensor) -> torch.Tensor:
+    """``F.linear(x, weight, bias)[n, idx[n]]`` from the N gathered weight
+    rows: N dot products instead of a vocab-wide GEMM.  Plain torch, fp32
+    accumulation as in the GEMM it stands for, result in x's dtype."""
+    out = (x.float() * weight[idx].float()).sum(-1) + bias[idx].float()
+    return out.to(x.dtype)
+
+
 ACT_CODES = {"none": 0, "gelu": 1, "gelu_new": 2, "relu": 3, "silu": 4}
 _ACT_FNS = {
     0: lambda y: y,

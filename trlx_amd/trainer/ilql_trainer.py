@@ -7,6 +7,7 @@ terminal reward on the last action) and the trainer (target-Q sync every
 ``steps_for_target_q_sync``, loss via ILQLConfig).
 """
 
+import os
 from typing import Union
 
 import numpy as np
@@ -14,7 +15,9 @@ import torch
 
 from ..data.configs import TRLConfig
 from ..data.ilql_types import ILQLBatch
-from ..models.modeling_ilql import AutoModelForCausalLMWithILQLHeads, ILQLConfig
+from ..models.modeling_ilql import (AutoModelForCausalLMWithILQLHeads, ILQLConfig,
+                                    ilql_actions)
+from ..parallel import topo
 from ..pipeline.offline_pipeline import ILQLRolloutStorage, tokenize_dialogue
 from ..trainer import register_trainer
 from ..utils import to_device
@@ -165,12 +168,21 @@ class ILQLTrainer(NativeRLTrainer):
                 states_ixs=batch.states_ixs,
             )
         else:
+            # opt-in (TRLX_AMD_FUSED_ILQL=1): heads and AWAC term reduced to
+            # the taken actions inside the model, no [N, V] forward tensors.
+            # Causal, non-pipelined, non-TP model only.
+            fused = (os.environ.get("TRLX_AMD_FUSED_ILQL") == "1"
+                     and topo.tp_size() == 1
+                     and isinstance(self.unwrapped_model, AutoModelForCausalLMWithILQLHeads))
             out = self.model(
                 input_ids=batch.input_ids,
                 attention_mask=batch.attention_mask,
                 actions_ixs=batch.actions_ixs,
                 states_ixs=batch.states_ixs,
+                **(dict(fused_actions=ilql_actions(batch)) if fused else {}),
             )
+            if getattr(out, "action_values", None) is not None:
+                return self.ilql.loss(out.action_values, batch)
         return self.ilql.loss((out.logits, (out.qs, out.target_qs, out.vs)), batch)
 
     def create_train_dataloader(self):
