@@ -23,6 +23,11 @@ std::vector<at::Tensor> gae(const at::Tensor& values, const at::Tensor& rewards,
 at::Tensor sum_count(const at::Tensor& x);
 at::Tensor normalize(const at::Tensor& x, const at::Tensor& mean, const at::Tensor& var,
                      bool shift_mean);
+std::vector<at::Tensor> ppo_loss(const at::Tensor& logprobs, const at::Tensor& values,
+                                 const at::Tensor& old_logprobs, const at::Tensor& old_values,
+                                 const at::Tensor& advantages, const at::Tensor& returns,
+                                 const at::Tensor& mask, double cliprange, double cliprange_value,
+                                 double vf_coef);
 at::Tensor gumbel_sample(const at::Tensor& logits, double temperature,
                          const c10::optional<at::Tensor>& thresholds, long seed, long offset);
 at::Tensor gumbel_sample_dev(const at::Tensor& logits, double temperature,
@@ -160,6 +165,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("gae", &gae);
   mod.def("sum_count", &sum_count);
   mod.def("normalize", &normalize);
+  mod.def("ppo_loss", &ppo_loss);
   mod.def("gumbel_sample", &gumbel_sample);
   mod.def("gumbel_sample_dev", &gumbel_sample_dev);
   mod.def("decode_prep", &decode_prep);

@@ -9,6 +9,9 @@ MI355X redesign notes:
 - GAE runs as the wave-parallel affine-scan HIP kernel (ops.gae) instead of a
   Python reverse loop; whitening uses the fused stats kernels + one RCCL
   all-reduce when distributed.
+- The clipped loss, its logged statistics and the gradients w.r.t. logprobs
+  and values are one single-workgroup kernel (ops.ppo_loss) on GPU fp32
+  inputs; the plain-torch body stays as ``PPOConfig._loss_eager``.
 - The hydra frozen branch re-runs only the top unfrozen blocks from the
   trunk's stashed hidden state: ``forward(..., return_ref_logits=True)`` gives
   policy logits, values, AND reference logits in ONE trunk pass (the reference
@@ -130,7 +133,31 @@ class PPOConfig(MethodConfig):
         returns: torch.Tensor,
         mask: torch.Tensor,
     ):
-        """Clipped surrogate PPO loss (reference modeling_ppo.py:175-238)."""
+        """Clipped surrogate PPO loss (reference modeling_ppo.py:175-238).
+
+        On GPU fp32 inputs the loss, all statistics and both gradients come
+        from the one-workgroup fused kernel (``ops.ppo_loss``);
+        ``TRLX_AMD_NO_FUSED_PPO_LOSS=1`` restores the eager body, which is
+        also the CPU path and the kernel's test reference."""
+        if ops.ppo_loss_fusable(logprobs, values, old_logprobs, old_values, advantages, returns, mask):
+            return ops.ppo_loss(
+                logprobs, values, old_logprobs, old_values, advantages, returns, mask,
+                self.cliprange, self.cliprange_value, self.vf_coef,
+            )
+        return self._loss_eager(logprobs, values, old_logprobs, old_values, advantages, returns, mask)
+
+    def _loss_eager(
+        self,
+        logprobs: torch.Tensor,
+        values: torch.Tensor,
+        old_logprobs: torch.Tensor,
+        old_values: torch.Tensor,
+        advantages: torch.Tensor,
+        returns: torch.Tensor,
+        mask: torch.Tensor,
+    ):
+        """The loss in plain torch ops: on a GPU about 155 elementwise and
+        reduction kernels per step, forward plus autograd's mirror."""
         values_clipped = torch.clamp(
             values, old_values - self.cliprange_value, old_values + self.cliprange_value
         )

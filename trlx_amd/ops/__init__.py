@@ -652,6 +652,76 @@ def whiten(xs: torch.Tensor, shift_mean: bool = True, distributed: bool = False,
 
 
 # --------------------------------------------------------------------------
+# fused PPO loss
+# --------------------------------------------------------------------------
+
+# What PPOConfig.loss returns, in its order: the layout of the kernel's
+# statistics vector (csrc/ppo_loss.hip, the O_* enum).
+PPO_LOSS_STAT_KEYS = (
+    "losses/total_loss", "losses/policy_loss", "losses/value_loss",
+    "values/mean", "values/min", "values/max", "values/std", "values/values_error", "values/clipfrac",
+    "old_values/mean", "old_values/min", "old_values/max", "old_values/std",
+    "returns/mean", "returns/min", "returns/max", "returns/std",
+    "policy/approx_kl", "policy/clipfrac", "ratio", "padding_percentage",
+)
+
+
+class _PPOLoss(torch.autograd.Function):
+    """The kernel already wrote d loss / d logprobs and d loss / d values for
+    an upstream gradient of 1 (stacked as one [2, B, R] tensor); backward is
+    ONE device-side multiply by the incoming gradient."""
+
+    @staticmethod
+    def forward(ctx, logprobs, values, old_logprobs, old_values, advantages, returns, mask,
+                cliprange, cliprange_value, vf_coef, ext):
+        loss, stats, grads = ext.ppo_loss(logprobs, values, old_logprobs, old_values, advantages,
+                                          returns, mask, cliprange, cliprange_value, vf_coef)
+        ctx.save_for_backward(grads)
+        ctx.mark_non_differentiable(stats)
+        return loss, stats
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_stats):
+        (grads,) = ctx.saved_tensors
+        g = grads * grad_loss
+        return (g[0] if ctx.needs_input_grad[0] else None,
+                g[1] if ctx.needs_input_grad[1] else None) + (None,) * 9
+
+
+def ppo_loss_fusable(logprobs, values, old_logprobs, old_values, advantages, returns, mask) -> bool:
+    """Does this call of ``PPOConfig.loss`` take the fused kernel?  GPU fp32
+    [B, R] inputs of one shape (any strides), an int64 mask, gradients wanted
+    for ``logprobs``/``values`` only, and ``TRLX_AMD_NO_FUSED_PPO_LOSS`` not 1."""
+    if os.environ.get("TRLX_AMD_NO_FUSED_PPO_LOSS") == "1":
+        return False
+    floats = (logprobs, values, old_logprobs, old_values, advantages, returns)
+    if not (logprobs.is_cuda and logprobs.dim() == 2 and logprobs.numel() > 0):
+        return False
+    if not all(t.is_cuda and t.dtype == torch.float32 and t.shape == logprobs.shape
+               and t.device == logprobs.device for t in floats):
+        return False
+    if not (mask.is_cuda and mask.dtype == torch.int64 and mask.shape == logprobs.shape
+            and mask.device == logprobs.device):
+        return False
+    if torch.is_grad_enabled() and any(t.requires_grad for t in floats[2:]):
+        return False
+    return _require_ext("ppo_loss") is not None
+
+
+def ppo_loss(logprobs, values, old_logprobs, old_values, advantages, returns, mask,
+             cliprange: float, cliprange_value: float, vf_coef: float):
+    """Clipped-surrogate PPO loss and its statistics from one kernel launch
+    (csrc/ppo_loss.hip).  Returns ``(loss, stats)`` as ``PPOConfig.loss``
+    does: ``loss`` a 0-dim tensor with the autograd node, ``stats`` a dict of
+    0-dim device tensors (views into one vector; no host synchronisation, so
+    the call can be captured into a graph)."""
+    ext = _require_ext("ppo_loss")
+    loss, stats = _PPOLoss.apply(logprobs, values, old_logprobs, old_values, advantages, returns,
+                                 mask, float(cliprange), float(cliprange_value), float(vf_coef), ext)
+    return loss, dict(zip(PPO_LOSS_STAT_KEYS, stats.unbind(0)))
+
+
+# --------------------------------------------------------------------------
 # sampling
 # --------------------------------------------------------------------------
 
