@@ -187,8 +187,10 @@ def test_gpu_logprobs(dtype, V):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize("H", [768, 4096, 5000])
+@pytest.mark.parametrize("H", [4, 100, 768, 4096, 4100, 5000])
 def test_gpu_rmsnorm(dtype, H):
+    # H=4: scalar tail only; 100: wave rows, 96 vector + 4 tail elements; 4096: the last
+    # wave-row H; 4100: block rows, 4096 vector + 4 tail elements
     torch.manual_seed(1)
     x = torch.randn(33, H).to(dtype).cuda().requires_grad_(True)
     w = (torch.randn(H) * 0.1 + 1).to(dtype).cuda().requires_grad_(True)
@@ -208,9 +210,11 @@ def test_gpu_rmsnorm(dtype, H):
 @pytest.mark.gpu
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("has_bias", [True, False])
-def test_gpu_layernorm(dtype, has_bias):
+@pytest.mark.parametrize("H", [100, 768, 4096, 4100, 4104])
+def test_gpu_layernorm(dtype, has_bias, H):
+    # wave rows up to H=4096 (100: with a scalar tail), block rows above (4100: with a
+    # tail, 4104: without)
     torch.manual_seed(2)
-    H = 768
     x = torch.randn(57, H).to(dtype).cuda().requires_grad_(True)
     w = (torch.randn(H) * 0.1 + 1).to(dtype).cuda().requires_grad_(True)
     b = (torch.randn(H) * 0.1).to(dtype).cuda().requires_grad_(True) if has_bias else None
@@ -233,11 +237,11 @@ def test_gpu_layernorm(dtype, has_bias):
 @pytest.mark.gpu
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("kind", ["rmsnorm", "layernorm"])
-def test_gpu_norm_add_fused(dtype, kind):
+@pytest.mark.parametrize("H", [100, 768, 4100])
+def test_gpu_norm_add_fused(dtype, kind, H):
     """Fused residual+norm (y, s) vs plain add + norm, fwd and bwd with a
     downstream use of s (the residual-stream continuation)."""
     torch.manual_seed(4)
-    H = 768
     x = torch.randn(41, H).to(dtype).cuda().requires_grad_(True)
     r = torch.randn(41, H).to(dtype).cuda().requires_grad_(True)
     w = (torch.randn(H) * 0.1 + 1).to(dtype).cuda().requires_grad_(True)
@@ -264,6 +268,71 @@ def test_gpu_norm_add_fused(dtype, kind):
     _assert_close(r.grad.cpu(), rr.grad, atol=atol, name=f"{kind}_add dres")
     _assert_close(w.grad.cpu(), wr.grad, atol=max(atol, 0.3 if dtype == torch.bfloat16 else 1e-2),
                   name=f"{kind}_add dw")
+    if kind == "layernorm":
+        _assert_close(b.grad.cpu(), br.grad, atol=max(atol, 0.3 if dtype == torch.bfloat16 else 1e-2),
+                      name=f"{kind}_add db")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["rmsnorm", "layernorm"])
+@pytest.mark.parametrize("N,H", [(0, 768), (1, 768), (9, 100), (8193, 100), (2049, 4100)])
+def test_gpu_norm_row_counts(kind, N, H):
+    """Row counts around the grids, fp32, forward and backward vs the reference:
+    no rows (nothing launched, zero dw/db); one row; 9 rows of wave-owned rows
+    (two full four-row blocks and a partial one); 8193 and 2049 rows, one more
+    than 2048 blocks hold, so the wave and the block grid-stride loops run (the
+    backward's too).  bf16 is left to the tests above: at N >= 2049 rounding
+    the exact dw to bf16 already misses their atol."""
+    gen = torch.Generator().manual_seed(6)
+    x = torch.randn(N, H, generator=gen).cuda().requires_grad_(True)
+    w = (torch.randn(H, generator=gen) * 0.1 + 1).cuda().requires_grad_(True)
+    b = (torch.randn(H, generator=gen) * 0.1).cuda().requires_grad_(True)
+    xr, wr, br = (t.detach().cpu().requires_grad_(True) for t in (x, w, b))
+    if kind == "rmsnorm":
+        y, yr = ops.rmsnorm(x, w), reference.rmsnorm(xr, wr)
+    else:
+        y, yr = ops.layernorm(x, w, b), reference.layernorm(xr, wr, br)
+    g = torch.randn(N, H, generator=gen)
+    y.backward(g.cuda())
+    yr.backward(g)
+    assert y.shape == (N, H) and x.grad.shape == (N, H)
+    if N > 0:  # (the helper takes the max of the difference)
+        _assert_close(y.cpu(), yr, atol=1e-5, name=f"{kind} fwd")
+        _assert_close(x.grad.cpu(), xr.grad, atol=1e-3, name=f"{kind} dx")
+    _assert_close(w.grad.cpu(), wr.grad, atol=1e-2, name=f"{kind} dw")
+    if kind == "layernorm":
+        _assert_close(b.grad.cpu(), br.grad, atol=1e-2, name=f"{kind} db")
+    if N == 0:
+        assert not w.grad.any() and (kind == "rmsnorm" or not b.grad.any())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["rmsnorm", "layernorm"])
+def test_gpu_norm_bwd_checks_inputs(kind):
+    """The backward entry points check what the forward checks: a statistics
+    vector of N + 1 elements and a non-contiguous x raise, valid input returns."""
+    from trlx_amd import _C as ext
+
+    N, H = 4, 64
+    gen = torch.Generator().manual_seed(7)
+    x, dy = torch.randn(N, H, generator=gen).cuda(), torch.randn(N, H, generator=gen).cuda()
+    w = torch.ones(H).cuda()
+    if kind == "rmsnorm":
+        stats = ext.rmsnorm_fwd(x, w, 1e-6, None)[1:]
+        bwd, n_out = ext.rmsnorm_bwd, 2
+    else:
+        stats = ext.layernorm_fwd(x, w, None, 1e-5, None)[1:]
+        bwd, n_out = ext.layernorm_bwd, 3
+    assert len(bwd(x, w, *stats, dy, None)) == n_out
+    for i in range(len(stats)):
+        longer = list(stats)
+        longer[i] = torch.zeros(N + 1, device="cuda")
+        with pytest.raises(RuntimeError, match="statistics"):
+            bwd(x, w, *longer, dy, None)
+    x_t = torch.randn(H, N, generator=gen).cuda().t()  # [N, H], strides (1, N)
+    assert not x_t.is_contiguous()
+    with pytest.raises(RuntimeError, match="contiguous"):
+        bwd(x_t, w, *stats, dy, None)
 
 
 def test_cpu_norm_add_matches_unfused():

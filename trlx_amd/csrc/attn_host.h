@@ -10,6 +10,8 @@
 #include <type_traits>
 #include <utility>
 
+#include "dispatch.h"  // dispatch_bool
+
 // ---- head dims ---------------------------------------------------------------
 
 // The head dims each kernel family is instantiated for: the one place on the
@@ -23,14 +25,6 @@ constexpr HeadDims<32, 64, 96, 128, 256> kDecodeHeadDims{};  // attention_decode
 constexpr HeadDims<64, 128> kSeq2SeqDecodeHeadDims{};        // s2s_decode.hip (T5 per-token step)
 
 // ---- runtime value -> compile-time constant ------------------------------------
-
-// f(std::true_type{}) or f(std::false_type{}): inside a generic lambda the
-// argument's ::value is a constant expression, usable as a template argument.
-template <typename F>
-void dispatch_bool(bool b, F&& f) {
-  if (b) f(std::true_type{});
-  else f(std::false_type{});
-}
 
 // f(std::integral_constant<int, D>{}) for the listed dim equal to D; any other
 // D raises "<op>: head dim must be 64, 96, 128 or 256, got <D>" (the list is Ds).

@@ -396,58 +396,52 @@ def _addmm_act_ok() -> bool:
 # --------------------------------------------------------------------------
 
 
-class _RMSNorm(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, weight, eps, ext):
-        x2d = x.reshape(-1, x.shape[-1]).contiguous()
-        out, inv_rms = ext.rmsnorm_fwd(x2d, weight, eps, None)
-        ctx.save_for_backward(x2d, weight, inv_rms)
-        ctx.x_shape = x.shape
-        return out.view(x.shape)
+class _Norm(torch.autograd.Function):
+    """RMSNorm (``kind`` "rmsnorm", no bias) or LayerNorm ("layernorm") of the
+    last dim, alone or with the residual add fused in.
+
+    With ``res``: (y, s) = (norm(x + res), x + res).  The backward adds the
+    residual-stream gradient ``ds`` into dx inside the norm-backward kernel, so
+    the whole residual connection costs zero extra elementwise kernels.  dx
+    and dres are the SAME tensor (aliasing is safe: autograd accumulates grads
+    out-of-place).  Saved for the backward: the normalized input (x, or s with
+    ``res``), the weight and the row statistics the kernel wrote."""
 
     @staticmethod
-    def backward(ctx, grad_out):
-        x2d, weight, inv_rms = ctx.saved_tensors
-        ext = _require_ext("rmsnorm")
-        dx, dw = ext.rmsnorm_bwd(x2d, weight, inv_rms,
-                                 grad_out.reshape(x2d.shape).contiguous(), None)
-        return dx.view(ctx.x_shape), dw, None, None
+    def forward(ctx, kind, x, res, weight, bias, eps, ext):
+        x2d = x.reshape(-1, x.shape[-1]).contiguous()
+        r2d = res.reshape(x2d.shape).contiguous() if res is not None else None
+        if kind == "rmsnorm":
+            out, *stats = ext.rmsnorm_fwd(x2d, weight, eps, r2d)
+        else:
+            out, *stats = ext.layernorm_fwd(x2d, weight, bias, eps, r2d)
+        s = stats.pop() if res is not None else x2d
+        ctx.save_for_backward(s, weight, *stats)
+        ctx.kind = kind
+        ctx.x_shape = x.shape
+        ctx.has_res = res is not None
+        ctx.has_bias = bias is not None
+        out = out.view(x.shape)
+        return (out, s.view(x.shape)) if res is not None else out
+
+    @staticmethod
+    def backward(ctx, grad_out, grad_s=None):
+        s2d, weight, *stats = ctx.saved_tensors
+        ext = _require_ext(ctx.kind)
+        bwd = ext.rmsnorm_bwd if ctx.kind == "rmsnorm" else ext.layernorm_bwd
+        gs = grad_s.reshape(s2d.shape).contiguous() if grad_s is not None else None
+        dx, dw, *db = bwd(s2d, weight, *stats, grad_out.reshape(s2d.shape).contiguous(), gs)
+        dx = dx.view(ctx.x_shape)
+        return (None, dx, dx if ctx.has_res else None, dw, db[0] if ctx.has_bias else None,
+                None, None)
 
 
 def rmsnorm(x: torch.Tensor, weight: torch.Tensor, eps: float = 1e-6) -> torch.Tensor:
     if x.is_cuda:
         ext = _require_ext("rmsnorm")
         if ext is not None:
-            return _RMSNorm.apply(x, weight, eps, ext)
+            return _Norm.apply("rmsnorm", x, None, weight, None, eps, ext)
     return reference.rmsnorm(x, weight, eps)
-
-
-class _RMSNormAdd(torch.autograd.Function):
-    """Residual-add fused into RMSNorm: (y, s) = (rmsnorm(x + res), x + res).
-
-    The backward adds the residual-stream gradient ``ds`` into dx inside the
-    norm-backward kernel, so the whole residual connection costs zero extra
-    elementwise kernels.  dx and dres are the SAME tensor (aliasing is safe:
-    autograd accumulates grads out-of-place)."""
-
-    @staticmethod
-    def forward(ctx, x, res, weight, eps, ext):
-        x2d = x.reshape(-1, x.shape[-1]).contiguous()
-        r2d = res.reshape(x2d.shape).contiguous()
-        out, inv_rms, s = ext.rmsnorm_fwd(x2d, weight, eps, r2d)
-        ctx.save_for_backward(s, weight, inv_rms)
-        ctx.x_shape = x.shape
-        return out.view(x.shape), s.view(x.shape)
-
-    @staticmethod
-    def backward(ctx, grad_out, grad_s):
-        s2d, weight, inv_rms = ctx.saved_tensors
-        ext = _require_ext("rmsnorm")
-        gs = grad_s.reshape(s2d.shape).contiguous() if grad_s is not None else None
-        dx, dw = ext.rmsnorm_bwd(s2d, weight, inv_rms,
-                                 grad_out.reshape(s2d.shape).contiguous(), gs)
-        dx = dx.view(ctx.x_shape)
-        return dx, dx, dw, None, None
 
 
 def rmsnorm_add(x: torch.Tensor, res: torch.Tensor, weight: torch.Tensor, eps: float = 1e-6):
@@ -455,28 +449,9 @@ def rmsnorm_add(x: torch.Tensor, res: torch.Tensor, weight: torch.Tensor, eps: f
     if x.is_cuda:
         ext = _require_ext("rmsnorm")
         if ext is not None:
-            return _RMSNormAdd.apply(x, res, weight, eps, ext)
+            return _Norm.apply("rmsnorm", x, res, weight, None, eps, ext)
     s = x + res
     return reference.rmsnorm(s, weight, eps), s
-
-
-class _LayerNorm(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, weight, bias, eps, ext):
-        x2d = x.reshape(-1, x.shape[-1]).contiguous()
-        out, mean, invstd = ext.layernorm_fwd(x2d, weight, bias, eps, None)
-        ctx.save_for_backward(x2d, weight, mean, invstd)
-        ctx.x_shape = x.shape
-        ctx.has_bias = bias is not None
-        return out.view(x.shape)
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        x2d, weight, mean, invstd = ctx.saved_tensors
-        ext = _require_ext("layernorm")
-        dx, dw, db = ext.layernorm_bwd(x2d, weight, mean, invstd,
-                                       grad_out.reshape(x2d.shape).contiguous(), None)
-        return dx.view(ctx.x_shape), dw, (db if ctx.has_bias else None), None, None
 
 
 def layernorm(
@@ -485,32 +460,8 @@ def layernorm(
     if x.is_cuda:
         ext = _require_ext("layernorm")
         if ext is not None:
-            return _LayerNorm.apply(x, weight, bias, eps, ext)
+            return _Norm.apply("layernorm", x, None, weight, bias, eps, ext)
     return reference.layernorm(x, weight, bias, eps)
-
-
-class _LayerNormAdd(torch.autograd.Function):
-    """Residual-add fused into LayerNorm (see _RMSNormAdd)."""
-
-    @staticmethod
-    def forward(ctx, x, res, weight, bias, eps, ext):
-        x2d = x.reshape(-1, x.shape[-1]).contiguous()
-        r2d = res.reshape(x2d.shape).contiguous()
-        out, mean, invstd, s = ext.layernorm_fwd(x2d, weight, bias, eps, r2d)
-        ctx.save_for_backward(s, weight, mean, invstd)
-        ctx.x_shape = x.shape
-        ctx.has_bias = bias is not None
-        return out.view(x.shape), s.view(x.shape)
-
-    @staticmethod
-    def backward(ctx, grad_out, grad_s):
-        s2d, weight, mean, invstd = ctx.saved_tensors
-        ext = _require_ext("layernorm")
-        gs = grad_s.reshape(s2d.shape).contiguous() if grad_s is not None else None
-        dx, dw, db = ext.layernorm_bwd(s2d, weight, mean, invstd,
-                                       grad_out.reshape(s2d.shape).contiguous(), gs)
-        dx = dx.view(ctx.x_shape)
-        return dx, dx, dw, (db if ctx.has_bias else None), None, None
 
 
 def layernorm_add(x: torch.Tensor, res: torch.Tensor, weight: torch.Tensor,
@@ -519,7 +470,7 @@ def layernorm_add(x: torch.Tensor, res: torch.Tensor, weight: torch.Tensor,
     if x.is_cuda:
         ext = _require_ext("layernorm")
         if ext is not None:
-            return _LayerNormAdd.apply(x, res, weight, bias, eps, ext)
+            return _Norm.apply("layernorm", x, res, weight, bias, eps, ext)
     s = x + res
     return reference.layernorm(s, weight, bias, eps), s
 
