@@ -22,7 +22,8 @@ from test_ilql_fused import loss_and_grads, ragged_ilql_batch, tiny_ilql_model
 pytestmark = pytest.mark.gpu
 
 # max |val - ref|, |lse - ref| over CASES measured 7.63e-6 (lse, case
-# (257, 1000, 192)); bound = 4x = 3.05e-5, rounded up to one digit
+# (257, 1000, 192); case (257, 1281, 64) measured 1.91e-6 and leaves the
+# maximum where it was); bound = 4x = 3.05e-5, rounded up to one digit
 FWD_BOUND = 4e-5
 BF16_ULP = 2.0 ** -7
 # tiny model, fused vs unfused: measured loss difference 5.91e-5 and worst
@@ -32,7 +33,10 @@ MODEL_LOSS_BOUND = 3e-4
 MODEL_GRAD_REL_BOUND = 4e-2
 MODEL_GRAD_COSINE = 0.99
 
-CASES = [(1, 256, 64), (255, 257, 64), (257, 1000, 192), (300, 513, 128)]
+# (257, 1281, 64): 2 x 6 = 12 workgroups, the smallest grid in which the XCD
+# remap of csrc/lm_tile.h takes both of its branches with a non-zero quotient
+# (q8 = 1, r8 = 4); one K-tile, ragged last row tile and last column tile
+CASES = [(1, 256, 64), (255, 257, 64), (257, 1000, 192), (300, 513, 128), (257, 1281, 64)]
 _cache = {}
 
 
@@ -140,8 +144,8 @@ def test_autograd_op_grads():
         assert rel <= BF16_ULP, name
 
 
-def test_old_entry_points_unchanged():
-    N, V, K = 300, 513, 128
+@pytest.mark.parametrize("N,V,K", CASES)
+def test_old_entry_points_unchanged(N, V, K):
     c = _case(N, V, K)
     ext = _ext()
     zb = torch.zeros_like(c["bias"])
@@ -160,6 +164,63 @@ def test_old_entry_points_unchanged():
     err = (old.float() - new.float()).abs()
     tol = FWD_BOUND * g.abs().max().item() + BF16_ULP * new.float().abs()
     assert (err <= tol).all()
+
+
+def test_empty_input():
+    """N = 0: every entry point of the two files returns the right shape and
+    dtype without a launch."""
+    ext = _ext()
+    V, K = 300, 64
+    x = torch.empty(0, K, device="cuda", dtype=torch.bfloat16)
+    w = torch.zeros(V, K, device="cuda", dtype=torch.bfloat16)
+    bias = torch.zeros(V, device="cuda")
+    idx = torch.empty(0, device="cuda", dtype=torch.long)
+    f = torch.empty(0, device="cuda")
+    outs = [ext.lm_logprobs_v2(x, w, idx), *ext.lm_logprobs_v2_with_lse(x, w, idx, True),
+            *ext.linear_gather_lse_fwd(x, w, bias, idx)]
+    for o in outs:
+        assert o.shape == (0,) and o.dtype == torch.float32
+    for dz in (ext.ce_dlogits(x, w, idx, f, f),
+               ext.linear_gather_lse_bwd(x, w, bias, idx, f, f, f)):
+        assert dz.shape == (0, V) and dz.dtype == torch.bfloat16
+
+
+def test_rejected_input():
+    ext = _ext()
+    N, V, K = 255, 257, 64
+    c = _case(N, V, K)
+    x, w, idx, lse, g = c["x"], c["w"], c["idx"], c["lse"], c["g_val"]
+    x96 = torch.zeros(N, 96, device="cuda", dtype=torch.bfloat16)
+    w96 = torch.zeros(V, 96, device="cuda", dtype=torch.bfloat16)
+    with pytest.raises(RuntimeError):
+        ext.lm_logprobs_v2(x96, w96, idx)
+    with pytest.raises(RuntimeError):
+        ext.ce_dlogits(x96, w96, idx, lse, g)
+    with pytest.raises(RuntimeError):
+        ext.ce_dlogits(x, w, idx.int(), lse, g)
+    with pytest.raises(RuntimeError):
+        ext.ce_dlogits(x, w, idx, lse[:-1].contiguous(), g)
+    with pytest.raises(RuntimeError):
+        ext.ce_dlogits(x, w, idx, lse, g.bfloat16())
+    lse2 = torch.stack([lse, lse], 1)[:, 0]
+    assert not lse2.is_contiguous() and torch.equal(lse2, lse)
+    with pytest.raises(RuntimeError):
+        ext.ce_dlogits(x, w, idx, lse2, g)
+    # the same operands, well-formed, are accepted
+    assert ext.ce_dlogits(x, w, idx, lse, g).shape == (N, V)
+
+
+def test_strided_dlp():
+    ext = _ext()
+    N, V, K = 255, 257, 64
+    c = _case(N, V, K)
+    long = torch.randn(2 * N, generator=torch.Generator().manual_seed(3)).cuda()
+    g = long[::2]
+    assert not g.is_contiguous() and g.dtype == torch.float32
+    got = ext.ce_dlogits(c["x"], c["w"], c["idx"], c["lse"], g)
+    want = ext.ce_dlogits(c["x"], c["w"], c["idx"], c["lse"], g.contiguous())
+    assert (want != 0).any()
+    assert torch.equal(got, want)
 
 
 def _gpu_model(two_qs=True):

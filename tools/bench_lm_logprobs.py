@@ -3,7 +3,7 @@
 Compares (on the PPO experience shapes):
   - unfused: hipBLASLt GEMM -> logits -> fused logprob-gather kernel
   - v1: single-buffered 128x128 MFMA tile kernel
-  - v2: 8-phase pipelined 256x256 MFMA kernel
+  - v2: minimum-2-phase pipelined 256x256 MFMA kernel
 
 Run on a GPU box:  python tools/bench_lm_logprobs.py
 """

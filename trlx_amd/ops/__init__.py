@@ -176,7 +176,7 @@ def lm_logprobs(hidden: torch.Tensor, weight: torch.Tensor, labels: torch.Tensor
             h = hidden.contiguous()
             if h.shape[1] % 64 == 0 and hasattr(ext, "lm_logprobs_v2") and \
                     os.environ.get("TRLX_AMD_LM_LOGPROBS_V1") != "1":
-                # 8-phase pipelined 256x256 MFMA kernel
+                # minimum-2-phase pipelined 256x256 MFMA kernel
                 return ext.lm_logprobs_v2(h, weight.contiguous(), labels.contiguous())
             return ext.lm_logprobs(h, weight.contiguous(), labels.contiguous())
     logits = hidden.float() @ weight.float().t()
