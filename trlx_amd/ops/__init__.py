@@ -783,10 +783,16 @@ def sample_token(
 ) -> torch.Tensor:
     """One fused sampling step [B, V] -> [B].
 
-    On GPU: Gumbel-max categorical sampling in a single pass (no softmax
-    materialization), counter-based RNG keyed by (seed, offset, row) for
-    per-DP-rank reproducibility.  top_k/top_p pre-filter runs tile-wise in
-    the same kernel via threshold select.
+    On GPU: Gumbel-max categorical sampling (no softmax materialization),
+    counter-based RNG keyed by (seed, offset, row, col) for per-DP-rank
+    reproducibility; ``offset`` may be a device int64 tensor, so captured
+    graphs draw fresh noise.  The unfiltered call is one pass of the
+    ``gumbel_sample`` kernel over the bf16/fp32 logits.  The filters are
+    library passes on an fp32 copy in front of that kernel: ``top_k`` takes
+    the k-th value from ``torch.topk`` and hands it over as a per-row
+    threshold; ``top_p`` sorts the row (or its top-k subset), masks by the
+    cumulative softmax and samples from the masked logits.  The keep rule
+    both filters implement is ``reference.select_threshold``.
     """
     if logits.is_cuda:
         ext = _require_ext("sample_token")

@@ -174,6 +174,41 @@ def sample_token(
     return torch.multinomial(probs, 1, generator=generator).squeeze(-1)
 
 
+def select_threshold(scores: torch.Tensor, top_k: int = 0, top_p: float = 1.0) -> torch.Tensor:
+    """The keep-threshold of every row of ``scores`` [B, V] under top-k then
+    top-p (HF order): a token is kept iff its score is >= the threshold, so
+    tied scores are kept together.  ``-inf`` scores are masked and never kept.
+
+    top-k (``0 < k < V``): t_k is the k-th largest finite score (all finite
+    scores stay when there are fewer than k).  top-p (``0 < p < 1``), over the
+    top-k survivors: with w = exp(s - max s) and Z = sum w, s_i is kept iff
+    the mass of the strictly larger survivors is <= p * Z (the maximum is
+    always kept).  The threshold is the smallest kept score; ``-inf`` when no
+    filter is active or the row has no finite score.  fp64 inside; returns
+    fp32 [B] (exactly one of the row's scores).
+    """
+    V = scores.shape[-1]
+    k_on = bool(top_k) and 0 < top_k < V
+    p_on = top_p is not None and 0.0 < top_p < 1.0
+    out = torch.full((scores.shape[0],), float("-inf"), dtype=torch.float32)
+    if not (k_on or p_on):
+        return out
+    for b, row in enumerate(scores.detach().cpu().double()):
+        s = row[row > float("-inf")].sort(descending=True).values
+        if s.numel() == 0:
+            continue
+        if k_on:
+            s = s[s >= s[min(top_k, s.numel()) - 1]]
+        if p_on:
+            w = torch.exp(s - s[0])
+            # mass strictly above each score: ties share the mass above their first member
+            first = torch.searchsorted(-s, -s, right=False)
+            above = (w.cumsum(0) - w)[first]
+            s = s[above <= top_p * w.sum()]
+        out[b] = s[-1].float()
+    return out
+
+
 def causal_softmax(
     scores: torch.Tensor, start_pos: int = 0, key_starts: Optional[torch.Tensor] = None
 ) -> torch.Tensor:
