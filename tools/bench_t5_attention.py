@@ -16,6 +16,10 @@ forward under no_grad: policy + value + frozen reference branch) and one train
 step (forward + backward, top decoder blocks unfrozen) of a t5-small-sized
 model are timed with the kernels off / on through the two switches.
 
+``--bias-grad`` runs one other A/B instead: self-attention forward+backward
+with a bias that wants a gradient, eager against ``bias_grad=True``
+(profiles/t5_bias_grad_notes.md).
+
     python tools/bench_t5_attention.py [--out profiles/t5_attention.json]
 
 Needs a GPU: there is no CPU fallback for a timing."""
@@ -168,6 +172,75 @@ def bench_bias_cost(name, B, H, D, Tq, Tk, causal, with_bias, args):
     return [row]
 
 
+def bench_bias_grad(args):
+    """``--bias-grad``: forward+backward of one self-attention layer whose bias
+    wants a gradient — what every self-attention layer of a fully unfrozen T5
+    costs.  Eager: the dense [1, H, T, T] bf16 bias is the leaf (its gradient
+    sums dS over the batch); kernels: the Toeplitz vector [H, L] is the leaf
+    and ``bias_grad=True`` runs the third backward kernel.  t5-small and
+    t5-base heads, B=32, with the peak memory of one call above the inputs."""
+    rows = []
+    B, D = 32, 64
+    for model, H in (("t5-small", 8), ("t5-base", 12)):
+        for T in (128, 512, 1024):
+            torch.manual_seed(0)
+            qg, kg, vg = (torch.randn(B, H, T, D, device=DEV).mul_(0.5).bfloat16()
+                          .requires_grad_(True) for _ in range(3))
+            dout = torch.randn(B, H, T, D, device=DEV).mul_(0.5).bfloat16()
+            key_mask = torch.ones(B, T, dtype=torch.uint8, device=DEV)
+            key_mask[::2, : T // 8] = 0
+            vec0, zero = ops.t5_rel_bias(torch.randn(32, H, device=DEV), T, T, 0, True)
+            vec = vec0.clone().requires_grad_(True)
+            dense = (ops.reference.gather_rel_bias(vec0, zero, T, T)[None].to(torch.bfloat16)
+                     .requires_grad_(True))
+            additive = AttnMask(key_mask, q_len=T, device=DEV).additive()
+            leaves = (qg, kg, vg, vec, dense)
+
+            def eager():
+                eager_attention(qg, kg, vg, dense, additive).backward(dout)
+
+            def flash():
+                ops.seq2seq_attention(qg, kg, vg, vec, zero, key_mask, False,
+                                      bias_grad=True).backward(dout)
+
+            def cleared(fn):
+                def run():
+                    fn()
+                    for t in leaves:
+                        t.grad = None
+                return run
+
+            peak, grads = {}, {}
+            for name, fn in (("eager", eager), ("flash", flash)):
+                torch.cuda.synchronize()
+                torch.cuda.reset_peak_memory_stats()
+                base = torch.cuda.memory_allocated()
+                fn()
+                torch.cuda.synchronize()
+                peak[name] = (torch.cuda.max_memory_allocated() - base) / 2**20
+                if name == "flash":
+                    grads[name] = vec.grad
+                else:  # the dense gradient summed along the diagonals, by autograd
+                    probe = vec0.clone().requires_grad_(True)
+                    ops.reference.gather_rel_bias(probe, zero, T, T).backward(
+                        dense.grad[0].float())
+                    grads[name] = probe.grad
+                for t in leaves:
+                    t.grad = None
+            res = alternate({"eager": cleared(eager), "flash": cleared(flash)}, args.windows,
+                            args.calls, args.warm, args.window_ms)
+            row = dict(kind="bias_grad", shape=f"{model} self T={T}", B=B, H=H, D=D, T=T,
+                       direction="forward+backward", eager_ms=summarize(res["eager"]),
+                       flash_ms=summarize(res["flash"]), calls_per_window=res["calls"],
+                       eager_peak_mib=peak["eager"], flash_peak_mib=peak["flash"],
+                       bias_grad_rel_diff=((grads["flash"] - grads["eager"]).abs().max()
+                                           / grads["eager"].abs().max()).item())
+            row["flash_over_eager"] = row["flash_ms"]["median"] / row["eager_ms"]["median"]
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    return rows
+
+
 def bench_model(args):
     """ppo_sentiments_t5 shape: t5-small-sized model, prompts 128, 25
     decoder tokens (start token + 24 new), chunk 16 for the experience pass,
@@ -230,17 +303,22 @@ def main():
                     help="least duration of a timed window; 0 times exactly --calls calls")
     ap.add_argument("--warm", type=int, default=5, help="warm calls before each window")
     ap.add_argument("--skip-model", action="store_true")
+    ap.add_argument("--bias-grad", action="store_true",
+                    help="only the trainable-bias A/B (bench_bias_grad)")
     ap.add_argument("--out", default=None, help="also write all rows to this JSON file")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_t5_attention: needs a GPU (no timing without one)")
     rows = []
-    for shape in SHAPES:
-        rows += bench_shape(*shape, args)
-    for shape in SHAPES[:3]:
-        rows += bench_bias_cost(*shape, args)
-    if not args.skip_model:
-        rows += bench_model(args)
+    if args.bias_grad:
+        rows += bench_bias_grad(args)
+    else:
+        for shape in SHAPES:
+            rows += bench_shape(*shape, args)
+        for shape in SHAPES[:3]:
+            rows += bench_bias_cost(*shape, args)
+        if not args.skip_model:
+            rows += bench_model(args)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:

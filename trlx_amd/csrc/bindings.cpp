@@ -135,6 +135,10 @@ std::vector<at::Tensor> flash_prefill_bwd(const at::Tensor& q, const at::Tensor&
                                           const c10::optional<at::Tensor>& alibi_slopes,
                                           const c10::optional<at::Tensor>& rel_bias, long bias_zero,
                                           const c10::optional<at::Tensor>& key_mask, bool causal);
+at::Tensor flash_bwd_dbias(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+                           const at::Tensor& out, const at::Tensor& dout, const at::Tensor& lse,
+                           const at::Tensor& rel_bias, long bias_zero,
+                           const c10::optional<at::Tensor>& key_mask, bool causal, double scale);
 at::Tensor seq2seq_decode_attention(const at::Tensor& q, const at::Tensor& k_new,
                                     const at::Tensor& v_new, at::Tensor& k_cache,
                                     at::Tensor& v_cache, const at::Tensor& cache_idx,
@@ -215,6 +219,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("scale"), py::arg("alibi_slopes") = py::none(),
           py::arg("rel_bias") = py::none(), py::arg("bias_zero") = 0,
           py::arg("key_mask") = py::none(), py::arg("causal") = true);
+  // gradient of the T5 relative-position bias vector (flash_bwd_dbias.hip)
+  mod.def("flash_bwd_dbias", &flash_bwd_dbias, py::arg("q"), py::arg("k"), py::arg("v"),
+          py::arg("out"), py::arg("dout"), py::arg("lse"), py::arg("rel_bias"),
+          py::arg("bias_zero"), py::arg("key_mask"), py::arg("causal"), py::arg("scale"));
   // the T5 per-token step (s2s_decode.hip): self-attention with in-place cache
   // append at a device-side index, and cross-attention under a key mask
   mod.def("seq2seq_decode_attention", &seq2seq_decode_attention, py::arg("q"), py::arg("k_new"),

@@ -39,7 +39,7 @@
 // Seq2seq (T5) modes at head dims 64 / 128 mirror the forward's: non-causal
 // (dKV sweeps every q-tile, dQ every key tile), rectangular Tq != Tk, the
 // Toeplitz relative bias and the arbitrary key mask inside the recomputed P.
-// The learned bias itself gets no gradient here.
+// The learned bias gets no gradient here: that is flash_bwd_dbias.hip.
 // Precondition (as for left-pad key_starts): K and V rows at masked keys are
 // FINITE.  A masked key enters dS as p * (dP - Drow) with p == 0, which is
 // exact for any finite K/V (the tests fill them with 1e4) and NaN for inf/NaN.

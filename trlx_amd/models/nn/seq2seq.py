@@ -12,13 +12,15 @@ seq2seq modes (``ops.seq2seq_attention``: non-causal, Toeplitz relative-
 position bias, arbitrary key mask, Tq != Tk) — bf16 on the GPU, head dim 64 or
 128, and ``ops.seq2seq_flash_enabled`` (on by default at both head dims, see
 profiles/t5_attention_notes.md; ``TRLX_AMD_NO_FLASH_PREFILL`` /
-``TRLX_AMD_NO_FLASH_TRAIN`` = 1 turn it off).  The kernels produce no gradient for the
-learned bias, so a layer whose bias table requires grad keeps the eager path
-(rocBLAS GEMMs + additive-bias softmax) under grad mode: with
-``num_layers_unfrozen > 0`` the tables are frozen and every attention
-qualifies; a fully unfrozen T5 trains its self-attention eager (its cross-
-attention and its no_grad passes still qualify).  Everything on CPU stays
-eager.  Dropout is not applied to attention probabilities on either path.
+``TRLX_AMD_NO_FLASH_TRAIN`` = 1 turn it off).  By default a layer whose bias table
+requires grad keeps the eager path (rocBLAS GEMMs + additive-bias softmax)
+under grad mode: with ``num_layers_unfrozen > 0`` the tables are frozen and
+every attention qualifies; a fully unfrozen T5 trains its self-attention eager
+(its cross-attention and its no_grad passes still qualify).  With
+``TRLX_AMD_FLASH_T5_BIAS_GRAD=1`` (``ops.seq2seq_bias_grad_enabled``, opt-in)
+those layers take the kernels too: the bias-gradient kernel
+(csrc/flash_bwd_dbias.hip) returns d loss / d bias vector per layer and
+autograd sums the layers into the table.  Everything on CPU stays eager.  Dropout is not applied to attention probabilities on either path.
 Norms, logprob gathers and sampling hit the gfx950 kernels.
 
 Generation: on the GPU in bf16 at a head dim in
@@ -250,19 +252,24 @@ class T5Attention(nn.Module):
     def _takes_kernel(self, q, k, v, mask, position_bias, past_kv, attn_mask) -> bool:
         """Does this call run in ``ops.seq2seq_attention``?  A full-sequence
         pass on the GPU in bf16 whose masks came as an ``AttnMask`` and whose
-        bias (if any) as a ``RelBias`` with a table that gets no gradient."""
+        bias (if any) as a ``RelBias``; a table that wants a gradient only
+        where ``ops.seq2seq_bias_grad_enabled`` (opt-in)."""
         if attn_mask is None or mask is not None or past_kv is not None:
             return False
         if not (_on_gpu_bf16(q) and _on_gpu_bf16(k) and _on_gpu_bf16(v)):
             return False
-        grad = torch.is_grad_enabled()
-        if position_bias is not None:
-            if not isinstance(position_bias, RelBias):
-                return False
-            if grad and position_bias.table.requires_grad:
-                return False  # the kernels produce no gradient for the learned bias
-        train = grad and (q.requires_grad or k.requires_grad or v.requires_grad)
+        if position_bias is not None and not isinstance(position_bias, RelBias):
+            return False
+        if self._wants_bias_grad(position_bias):
+            return ops.seq2seq_bias_grad_enabled(self.d_kv)
+        train = torch.is_grad_enabled() and (q.requires_grad or k.requires_grad
+                                             or v.requires_grad)
         return ops.seq2seq_flash_enabled(self.d_kv, train)
+
+    @staticmethod
+    def _wants_bias_grad(position_bias) -> bool:
+        return (isinstance(position_bias, RelBias) and torch.is_grad_enabled()
+                and position_bias.table.requires_grad)
 
     def forward(self, x, kv_input=None, mask=None, position_bias=None, past_kv=None,
                 attn_mask: Optional[AttnMask] = None):
@@ -300,9 +307,12 @@ class T5Attention(nn.Module):
         # T5: NO 1/sqrt(d) scaling
         if self._takes_kernel(q, k, v, mask, position_bias, past_kv, attn_mask):
             vec, zero = position_bias.vec() if position_bias is not None else (None, 0)
+            # a trainable table: vec hangs on it through the embedding lookup of
+            # t5_rel_bias, and each layer of the stack adds its own [H, L] gradient
+            extra = {"bias_grad": True} if self._wants_bias_grad(position_bias) else {}
             out = ops.seq2seq_attention(q, k, v, rel_bias=vec, bias_zero=zero,
                                         key_mask=attn_mask.uint8(), causal=attn_mask.causal,
-                                        start_pos=0, scale=1.0)
+                                        start_pos=0, scale=1.0, **extra)
             return self.o(out.transpose(1, 2).reshape(B, Tq, -1)), position_bias, new_kv
 
         scores = torch.matmul(q, k.transpose(-1, -2)).float()

@@ -84,6 +84,17 @@ def seq2seq_flash_enabled(head_dim: int, train: bool) -> bool:
                        SEQ2SEQ_FLASH_PREFILL_DEFAULT_DIMS, SEQ2SEQ_FLASH_TRAIN_DEFAULT_DIMS)
 
 
+def seq2seq_bias_grad_enabled(head_dim: int) -> bool:
+    """Does a T5 attention layer whose bias table is trainable take the kernels
+    under grad mode (``seq2seq_attention(..., bias_grad=True)``: the third
+    backward kernel produces the bias gradient)?  OPT-IN:
+    ``TRLX_AMD_FLASH_T5_BIAS_GRAD=1`` on top of ``seq2seq_flash_enabled(head_dim,
+    train=True)``; unset, such a layer keeps the eager path
+    (profiles/t5_bias_grad_notes.md has the A/B)."""
+    return (os.environ.get("TRLX_AMD_FLASH_T5_BIAS_GRAD") == "1"
+            and seq2seq_flash_enabled(head_dim, train=True))
+
+
 _EXT = None
 _EXT_TRIED = False
 _EXT_ERR: Optional[str] = None
@@ -970,9 +981,11 @@ class _FlashAttention(torch.autograd.Function):
     """Differentiable flash attention, causal (training prefill: start_pos ==
     0, Tk == T) and seq2seq alike: forward saves the per-row logsumexp,
     backward recomputes P from it tile-by-tile (csrc/flash_backward.hip) — the
-    [B,H,T,T] scores never materialize in either direction.  ``alibi_slopes``,
-    ``rel_bias`` and ``key_mask`` are constants here (not trainable; the
-    kernels produce no bias gradient)."""
+    [B,H,T,T] scores never materialize in either direction.  ``alibi_slopes``
+    and ``key_mask`` are constants here.  ``rel_bias`` is one too unless it
+    arrives requiring grad (``seq2seq_attention(bias_grad=True)``): then the
+    third backward kernel (csrc/flash_bwd_dbias.hip) returns its [Hq, L]
+    gradient, launched only when autograd asks for it."""
 
     @staticmethod
     def forward(ctx, q, k, v, key_starts, alibi_slopes, rel_bias, bias_zero, key_mask, causal,
@@ -982,8 +995,9 @@ class _FlashAttention(torch.autograd.Function):
         ctx.save_for_backward(q, k, v, out, lse)
         # the backward kernels have no start_pos: the bias index is
         # key - (start_pos + row) + bias_zero, so the offset folds into bias_zero
-        ctx.bwd_args = (key_starts, scale, alibi_slopes, rel_bias, bias_zero - start_pos,
-                        key_mask, causal)
+        ctx.bwd_args = (key_starts, scale, alibi_slopes,
+                        rel_bias.detach() if rel_bias is not None else None,
+                        bias_zero - start_pos, key_mask, causal)
         ctx.ext = ext
         return out
 
@@ -991,7 +1005,12 @@ class _FlashAttention(torch.autograd.Function):
     def backward(ctx, dout):
         q, k, v, out, lse = ctx.saved_tensors
         dq, dk, dv = ctx.ext.flash_prefill_bwd(q, k, v, out, dout, lse, *ctx.bwd_args)
-        return (dq, dk, dv) + (None,) * 9
+        dbias = None
+        if ctx.needs_input_grad[5]:
+            _, scale, _, rel_bias, bias_zero, key_mask, causal = ctx.bwd_args
+            dbias = ctx.ext.flash_bwd_dbias(q, k, v, out, dout, lse, rel_bias, bias_zero,
+                                            key_mask, causal, scale)
+        return (dq, dk, dv, None, None, dbias) + (None,) * 6
 
 
 def flash_attention(q, k, v, key_starts=None, scale: float = 1.0, alibi_slopes=None):
@@ -1026,7 +1045,8 @@ def t5_rel_bias(table: torch.Tensor, q_len: int, k_len: int, q_offset: int = 0,
 
 
 def seq2seq_attention(q, k, v, rel_bias=None, bias_zero: int = 0, key_mask=None,
-                      causal: bool = False, start_pos: int = 0, scale: float = 1.0):
+                      causal: bool = False, start_pos: int = 0, scale: float = 1.0,
+                      bias_grad: bool = False):
     """Flash attention for encoder-decoder models (csrc/flash_prefill.hip and
     flash_backward.hip in their seq2seq modes): q [B,Hq,Tq,D] bf16, k/v
     [B,Hkv,Tk,D], ``Tq != Tk`` allowed when not ``causal`` (cross-attention).
@@ -1038,14 +1058,20 @@ def seq2seq_attention(q, k, v, rel_bias=None, bias_zero: int = 0, key_mask=None,
     with no visible key returns zeros.  K and V rows at masked keys must be
     finite (they enter the backward as ``0 * x``).  Under ``no_grad``, or when no input requires grad, the
     forward-only kernel runs; otherwise the forward saves the row logsumexp
-    and the backward kernels produce dq/dk/dv.  ``rel_bias`` gets NO gradient
-    from the kernels, so a bias that requires grad is an error under grad mode
-    (models keep a trainable table on the eager path).  On CPU the fp32
-    reference runs."""
-    if rel_bias is not None and rel_bias.requires_grad and torch.is_grad_enabled():
+    and the backward kernels produce dq/dk/dv.  By default ``rel_bias`` gets
+    no gradient, so a bias that requires grad is an error under grad mode
+    (models keep a trainable table on the eager path).  ``bias_grad=True``
+    makes it a differentiable input instead: a third backward kernel
+    (csrc/flash_bwd_dbias.hip) sums dS along the diagonals into its [Hq, L]
+    fp32 gradient, deterministically, and autograd carries that through
+    ``t5_rel_bias`` to the table.  On CPU the fp32 reference runs (with
+    ``bias_grad`` autograd differentiates it with respect to the bias too)."""
+    wants_bias_grad = (rel_bias is not None and rel_bias.requires_grad
+                       and torch.is_grad_enabled())
+    if wants_bias_grad and not bias_grad:
         raise RuntimeError(
-            "seq2seq_attention: rel_bias requires grad, but the kernels produce no bias "
-            "gradient; detach it or keep this attention on the eager path")
+            "seq2seq_attention: rel_bias requires grad, but bias_grad is off; pass "
+            "bias_grad=True, detach it or keep this attention on the eager path")
     ext = _require_ext("seq2seq_attention")
     if ext is None or not q.is_cuda:
         return reference.seq2seq_attention(q, k, v, rel_bias, bias_zero, key_mask, causal,
@@ -1054,10 +1080,11 @@ def seq2seq_attention(q, k, v, rel_bias=None, bias_zero: int = 0, key_mask=None,
     if key_mask is not None:
         km = key_mask if key_mask.dtype == torch.uint8 else (key_mask != 0).to(torch.uint8)
         km = km.contiguous()
-    rb = rel_bias.detach() if rel_bias is not None else None
+    # detached unless its gradient is wanted: then autograd sees it as an input
+    rb = rel_bias if wants_bias_grad or rel_bias is None else rel_bias.detach()
     q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
     needs_grad = torch.is_grad_enabled() and (q.requires_grad or k.requires_grad
-                                              or v.requires_grad)
+                                              or v.requires_grad or wants_bias_grad)
     if not needs_grad:
         return ext.flash_prefill(q, k, v, None, int(start_pos), float(scale), 0, None, rb,
                                  int(bias_zero), km, bool(causal))
