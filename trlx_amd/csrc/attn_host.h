@@ -16,13 +16,15 @@
 
 // The head dims each kernel family is instantiated for: the one place on the
 // C++ side.  ops/__init__.py mirrors them as FLASH_HEAD_DIMS,
-// SEQ2SEQ_FLASH_HEAD_DIMS, DECODE_HEAD_DIMS and SEQ2SEQ_DECODE_HEAD_DIMS.
+// SEQ2SEQ_FLASH_HEAD_DIMS, DECODE_HEAD_DIMS, SEQ2SEQ_DECODE_HEAD_DIMS and
+// GQA_DECODE_HEAD_DIMS.
 template <int... Ds>
 struct HeadDims {};
 constexpr HeadDims<64, 96, 128, 256> kFlashHeadDims{};       // flash fwd + bwd
 constexpr HeadDims<64, 128> kSeq2SeqFlashHeadDims{};         // their seq2seq modes
 constexpr HeadDims<32, 64, 96, 128, 256> kDecodeHeadDims{};  // attention_decode, fused
 constexpr HeadDims<64, 128> kSeq2SeqDecodeHeadDims{};        // s2s_decode.hip (T5 per-token step)
+constexpr HeadDims<64, 128> kGqaDecodeHeadDims{};            // attn_decode_gqa.hip (group per block)
 
 // ---- runtime value -> compile-time constant ------------------------------------
 

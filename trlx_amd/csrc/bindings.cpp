@@ -53,6 +53,10 @@ at::Tensor attention_decode(const at::Tensor& q, const at::Tensor& kc, const at:
                             const at::Tensor& seq_lens, double scale,
                             const c10::optional<at::Tensor>& seq_starts,
                             const c10::optional<at::Tensor>& alibi_slopes);
+at::Tensor attention_decode_gqa(const at::Tensor& q, const at::Tensor& kc, const at::Tensor& vc,
+                                const at::Tensor& seq_lens, double scale,
+                                const c10::optional<at::Tensor>& seq_starts,
+                                const c10::optional<at::Tensor>& alibi_slopes, long num_splits);
 at::Tensor lm_logprobs_v2(const at::Tensor& hidden, const at::Tensor& weight,
                           const at::Tensor& labels);
 at::Tensor skinny_gemm(const at::Tensor& a, const at::Tensor& w,
@@ -180,6 +184,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("attention_decode", &attention_decode, py::arg("q"), py::arg("k_cache"),
           py::arg("v_cache"), py::arg("seq_lens"), py::arg("scale"), py::arg("seq_starts"),
           py::arg("alibi_slopes") = py::none());
+  mod.def("attention_decode_gqa", &attention_decode_gqa, py::arg("q"), py::arg("k_cache"),
+          py::arg("v_cache"), py::arg("seq_lens"), py::arg("scale"), py::arg("seq_starts"),
+          py::arg("alibi_slopes") = py::none(), py::arg("num_splits") = 0);
   mod.def("fused_adamw", &fused_adamw);
   mod.def("lm_logprobs", &lm_logprobs);
   mod.def("lm_logprobs_v2", &lm_logprobs_v2);

@@ -47,6 +47,10 @@ SEQ2SEQ_FLASH_TRAIN_DEFAULT_DIMS = (64, 128)
 # in attn_host.h): seq2seq_decode_attention / seq2seq_cross_decode_attention.
 SEQ2SEQ_DECODE_HEAD_DIMS = (64, 128)
 
+# Grouped-query decode attention (csrc/attn_decode_gqa.hip; kGqaDecodeHeadDims in
+# attn_host.h): one block per KV head and chunk of 16 query heads.
+GQA_DECODE_HEAD_DIMS = (64, 128)
+
 
 def _flash_gate(head_dim: int, train: bool, built, prefill_default, train_default) -> bool:
     """The gate behind ``flash_enabled`` / ``seq2seq_flash_enabled``: ``built``
@@ -93,6 +97,15 @@ def seq2seq_bias_grad_enabled(head_dim: int) -> bool:
     (profiles/t5_bias_grad_notes.md has the A/B)."""
     return (os.environ.get("TRLX_AMD_FLASH_T5_BIAS_GRAD") == "1"
             and seq2seq_flash_enabled(head_dim, train=True))
+
+
+def gqa_decode_enabled(head_dim: int, group: int) -> bool:
+    """Does ``attention_decode`` take the grouped-query kernel for ``group`` =
+    Hq / Hkv query heads per KV head?  OPT-IN until its end-to-end A/B exists
+    (profiles/gqa_decode_notes.md): ``TRLX_AMD_GQA_DECODE=1``, the extension
+    loaded, ``group >= 2`` and a head dim in ``GQA_DECODE_HEAD_DIMS``."""
+    return (os.environ.get("TRLX_AMD_GQA_DECODE") == "1" and group >= 2
+            and head_dim in GQA_DECODE_HEAD_DIMS and extension_available())
 
 
 _EXT = None
@@ -881,6 +894,8 @@ def attention_decode(
     scale: float,
     seq_starts: Optional[torch.Tensor] = None,
     alibi_slopes: Optional[torch.Tensor] = None,
+    grouped: Optional[bool] = None,
+    num_splits: int = 0,
 ) -> torch.Tensor:
     """Fused decode attention: q [B, Hq, 1, D] vs cache [B, Hkv, S, D]
     with per-row valid key range [seq_starts[b], seq_lens[b]) -> [B, Hq, 1, D]
@@ -890,11 +905,27 @@ def attention_decode(
     [B, H, S] score materialization.  ``alibi_slopes`` [Hq] fp32 (one slope
     per QUERY head) adds ``slope[h] * (key - seq_starts[b])`` to the scaled
     scores (Bloom).
+
+    ``grouped`` picks the kernel on the GPU: ``False`` the block-per-query-head
+    kernel, ``True`` the grouped-query kernel (csrc/attn_decode_gqa.hip: the
+    query heads of a KV head share one block, so its K/V rows are read once
+    per group; bf16, Hq / Hkv >= 2, D in ``GQA_DECODE_HEAD_DIMS`` — anything
+    else raises), ``None`` follows ``gqa_decode_enabled``.  ``num_splits`` is
+    that kernel's number of key splits: 0 lets it choose from the static
+    sizes, a positive value forces it.  On CPU both are ignored.
     """
     if q.is_cuda:
         ext = _require_ext("attention_decode")
         if ext is not None:
             ss = None if seq_starts is None else seq_starts.to(torch.int32).contiguous()
+            if grouped is None:
+                grouped = gqa_decode_enabled(q.shape[-1], q.shape[1] // k_cache.shape[1])
+            if grouped:
+                return ext.attention_decode_gqa(
+                    q.contiguous(), k_cache.contiguous(), v_cache.contiguous(),
+                    seq_lens.to(torch.int32).contiguous(), scale, ss, alibi_slopes,
+                    int(num_splits),
+                )
             return ext.attention_decode(
                 q.contiguous(), k_cache.contiguous(), v_cache.contiguous(),
                 seq_lens.to(torch.int32).contiguous(), scale, ss, alibi_slopes,
