@@ -16,6 +16,9 @@ std::vector<at::Tensor> layernorm_bwd(const at::Tensor& x, const at::Tensor& w,
                                       const at::Tensor& mean, const at::Tensor& invstd,
                                       const at::Tensor& dy,
                                       const c10::optional<at::Tensor>& dres);
+at::Tensor gated_act_fwd(const at::Tensor& g, const c10::optional<at::Tensor>& u, long act);
+std::vector<at::Tensor> gated_act_bwd(const at::Tensor& g, const c10::optional<at::Tensor>& u,
+                                      const at::Tensor& dh, long act);
 at::Tensor rope_fwd(const at::Tensor& x, const at::Tensor& cos, const at::Tensor& sin,
                     const at::Tensor& pos, bool interleaved, bool inverse, long rot);
 std::vector<at::Tensor> gae(const at::Tensor& values, const at::Tensor& rewards, double gamma,
@@ -169,6 +172,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("rmsnorm_bwd", &rmsnorm_bwd);
   mod.def("layernorm_fwd", &layernorm_fwd);
   mod.def("layernorm_bwd", &layernorm_bwd);
+  // h = act(g) * u and its backward (gated_act.hip); u = None: g is the fused [N, 2I]
+  mod.def("gated_act_fwd", &gated_act_fwd, py::arg("g"), py::arg("u"), py::arg("act"));
+  mod.def("gated_act_bwd", &gated_act_bwd, py::arg("g"), py::arg("u"), py::arg("dh"),
+          py::arg("act"));
   mod.def("rope_fwd", &rope_fwd);
   mod.def("gae", &gae);
   mod.def("sum_count", &sum_count);

@@ -340,7 +340,9 @@ class T5FFN(nn.Module):
         self.gated = cfg.is_gated
 
     def forward(self, x):
-        if self.gated:
+        if self.gated and ops.gated_act_enabled():
+            h = ops.gated_act(self.wi_0(x), self.wi_1(x), act="gelu_new")
+        elif self.gated:
             h = F.gelu(self.wi_0(x), approximate="tanh") * self.wi_1(x)
         else:
             h = F.relu(self.wi(x))

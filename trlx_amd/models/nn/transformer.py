@@ -362,13 +362,18 @@ class MLP(nn.Module):
                 self.fc_in = nn.Linear(cfg.hidden_size, i, bias=cfg.mlp_bias)
             self.down_proj = nn.Linear(i, cfg.hidden_size, bias=cfg.mlp_bias)
         self.act = _ACTS[cfg.activation]
+        self.act_name = cfg.activation
         self.act_code = ops.ACT_CODES.get(cfg.activation)
         self.isize = i // tp
 
     def forward(self, x):
         if self.swiglu:
-            gu = dense(self.gate_up_proj, x)
-            return dense(self.down_proj, self.act(gu[..., : self.isize]) * gu[..., self.isize :])
+            gu = dense(self.gate_up_proj, x)  # [..., gate_local | up_local], also under TP
+            if ops.gated_act_enabled():
+                h = ops.gated_act(gu, act=self.act_name)
+            else:
+                h = self.act(gu[..., : self.isize]) * gu[..., self.isize :]
+            return dense(self.down_proj, h)
         if self.act_code is None:
             return dense(self.down_proj, self.act(dense(self.fc_in, x)))
         return dense(self.down_proj, dense(self.fc_in, x, self.act_code, self.act))

@@ -500,6 +500,74 @@ def layernorm_add(x: torch.Tensor, res: torch.Tensor, weight: torch.Tensor,
 
 
 # --------------------------------------------------------------------------
+# gated MLP activation (SwiGLU / GeGLU)
+# --------------------------------------------------------------------------
+
+# The activations csrc/gated_act.hip is instantiated for (codes: ACT_CODES), and
+# the columns one of its blocks owns: shapes around a multiple of it exercise
+# the full-chunk-plus-tail path.
+GATED_ACTS = ("silu", "gelu_new", "gelu")
+GATED_ACT_CHUNK = 4096
+
+
+def gated_act_enabled() -> bool:
+    """Do the gated MLPs (``MLP`` with ``cfg.swiglu``, the gated ``T5FFN``) call
+    ``gated_act``?  OPT-IN until its end-to-end A/B exists
+    (profiles/gated_act_notes.md): ``TRLX_AMD_FUSED_GATED_ACT=1``.  Unset, they
+    keep their eager line and launch exactly the kernels they launched before."""
+    return os.environ.get("TRLX_AMD_FUSED_GATED_ACT") == "1"
+
+
+class _GatedAct(torch.autograd.Function):
+    """h = act(gate) * up over 2-D inputs; ``up`` None means ``gate`` is the
+    fused [N, 2I] (gate | up).  Saved for the backward: the input tensor(s),
+    nothing else — act(gate) is recomputed there.  The backward returns one
+    fresh [N, 2I] d_gate_up for the fused form (each half written once by the
+    kernel), (dgate, dup) otherwise."""
+
+    @staticmethod
+    def forward(ctx, gate, up, code, ext):
+        ctx.save_for_backward(*((gate,) if up is None else (gate, up)))
+        ctx.code = code
+        return ext.gated_act_fwd(gate, up, code)
+
+    @staticmethod
+    def backward(ctx, dh):
+        gate, *up = ctx.saved_tensors
+        ext = _require_ext("gated_act")
+        grads = ext.gated_act_bwd(gate, up[0] if up else None, dh.contiguous(), ctx.code)
+        return grads[0], (grads[1] if up else None), None, None
+
+
+def gated_act(gate: torch.Tensor, up: Optional[torch.Tensor] = None,
+              act: str = "silu") -> torch.Tensor:
+    """The gated MLP activation ``act(g) * u`` (SwiGLU, GeGLU).  With ``up``:
+    ``g = gate``, ``u = up``, two tensors [..., I] of one shape.  Without:
+    ``gate`` is the fused projection output [..., 2I], ``g`` its first half and
+    ``u`` its second.  Returns [..., I].
+
+    GPU, ``act`` in ``GATED_ACTS``, bf16 or fp32: one kernel forward and one
+    backward (csrc/gated_act.hip) that read the halves in place — no slice
+    copies, no second saved activation, no zero-filled slice gradients — with
+    fp32 math and one rounding per output.  CPU, or any other activation:
+    ``reference.gated_act``, the eager expression in the input dtype."""
+    if gate.is_cuda and act in GATED_ACTS:
+        ext = _require_ext("gated_act")
+        if ext is not None:
+            def rows(t):
+                t = t.reshape(-1, t.shape[-1])
+                return t if t.stride(-1) == 1 else t.contiguous()
+
+            if up is not None and up.shape != gate.shape:
+                raise ValueError(f"gated_act: gate {tuple(gate.shape)} and up "
+                                 f"{tuple(up.shape)} must have one shape")
+            out = _GatedAct.apply(rows(gate), None if up is None else rows(up),
+                                  ACT_CODES[act], ext)
+            return out.view(*gate.shape[:-1], out.shape[-1])
+    return reference.gated_act(gate, up, act)
+
+
+# --------------------------------------------------------------------------
 # RoPE
 # --------------------------------------------------------------------------
 

@@ -41,6 +41,26 @@ def layernorm(
     return out.to(dtype)
 
 
+_GATED_ACT_FNS = {
+    "gelu": torch.nn.functional.gelu,
+    "gelu_new": lambda x: torch.nn.functional.gelu(x, approximate="tanh"),
+    "relu": torch.nn.functional.relu,
+    "silu": torch.nn.functional.silu,
+}
+
+
+def gated_act(gate: torch.Tensor, up: Optional[torch.Tensor] = None,
+              act: str = "silu") -> torch.Tensor:
+    """``act(g) * u`` in the input dtype: ``g, u = gate, up``, or the two halves
+    of a fused ``gate`` [..., 2I] when ``up`` is None.  The expression the gated
+    MLPs spell out themselves when ``ops.gated_act_enabled()`` is off."""
+    fn = _GATED_ACT_FNS[act]
+    if up is None:
+        i = gate.shape[-1] // 2
+        return fn(gate[..., :i]) * gate[..., i:]
+    return fn(gate) * up
+
+
 def rope_cos_sin(
     seq_len: int,
     dim: int,
