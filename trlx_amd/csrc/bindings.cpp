@@ -19,6 +19,9 @@ std::vector<at::Tensor> layernorm_bwd(const at::Tensor& x, const at::Tensor& w,
 at::Tensor gated_act_fwd(const at::Tensor& g, const c10::optional<at::Tensor>& u, long act);
 std::vector<at::Tensor> gated_act_bwd(const at::Tensor& g, const c10::optional<at::Tensor>& u,
                                       const at::Tensor& dh, long act);
+at::Tensor lora_shrink(const at::Tensor& x, const at::Tensor& wt, double alpha);
+at::Tensor lora_expand(const at::Tensor& base, const at::Tensor& t, const at::Tensor& wt,
+                       double alpha, at::Tensor out);
 at::Tensor rope_fwd(const at::Tensor& x, const at::Tensor& cos, const at::Tensor& sin,
                     const at::Tensor& pos, bool interleaved, bool inverse, long rot);
 std::vector<at::Tensor> gae(const at::Tensor& values, const at::Tensor& rewards, double gamma,
@@ -176,6 +179,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("gated_act_fwd", &gated_act_fwd, py::arg("g"), py::arg("u"), py::arg("act"));
   mod.def("gated_act_bwd", &gated_act_bwd, py::arg("g"), py::arg("u"), py::arg("dh"),
           py::arg("act"));
+  // the LoRA adapter GEMMs (lora.hip): T = alpha x wt^T with wt [r, C], and
+  // out = base + alpha t wt^T with wt [C, r]; out may be base
+  mod.def("lora_shrink", &lora_shrink, py::arg("x"), py::arg("wt"), py::arg("alpha"));
+  mod.def("lora_expand", &lora_expand, py::arg("base"), py::arg("t"), py::arg("wt"),
+          py::arg("alpha"), py::arg("out"));
   mod.def("rope_fwd", &rope_fwd);
   mod.def("gae", &gae);
   mod.def("sum_count", &sum_count);

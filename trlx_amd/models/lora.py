@@ -28,6 +28,8 @@ from typing import Dict, List, Optional
 import torch
 import torch.nn as nn
 
+from trlx_amd import ops
+
 DEFAULT_TARGETS = ["qkv_proj", "o_proj", "fc_in", "gate_up_proj", "down_proj"]
 
 
@@ -52,6 +54,12 @@ class LoRALinear(nn.Module):
             p.requires_grad_(False)
 
     def forward(self, x):
+        if (self.enabled and ops.lora_enabled() and ops.lora_fusable(x, self.base, self.r)
+                and self.lora_A.dtype == x.dtype):
+            # base GEMM and adapter as one op (csrc/lora.hip); opt-in
+            xa = self.dropout(x) if self.dropout is not None else None
+            return ops.lora_linear(x, self.base.weight, self.base.bias, self.lora_A,
+                                   self.lora_B, self.scaling, x_lora=xa)
         y = self.base(x)
         if not self.enabled:
             return y

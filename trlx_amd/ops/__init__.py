@@ -568,6 +568,107 @@ def gated_act(gate: torch.Tensor, up: Optional[torch.Tensor] = None,
 
 
 # --------------------------------------------------------------------------
+# LoRA linear
+# --------------------------------------------------------------------------
+
+# The ranks csrc/lora.hip serves, and the columns of X one block of lora_shrink
+# covers before the read is split across blocks (fp32 slabs and a fixed-order
+# sum): a small N with an inner dim of 2 * LORA_SPLIT_COLS or more is split.
+LORA_MAX_RANK = 64
+LORA_SPLIT_COLS = 1024
+
+
+def lora_enabled() -> bool:
+    """Does ``LoRALinear`` call ``lora_linear``?  OPT-IN until its end-to-end A/B
+    exists (profiles/lora_notes.md): ``TRLX_AMD_FUSED_LORA=1``.  Unset, the
+    module keeps its eager lines and launches exactly the kernels it launched
+    before."""
+    return os.environ.get("TRLX_AMD_FUSED_LORA") == "1"
+
+
+def _lora_shapes_ok(K: int, O: int, r: int) -> bool:
+    return 1 <= r <= LORA_MAX_RANK and K % 8 == 0 and O % 8 == 0 and K > 0 and O > 0
+
+
+def lora_fusable(x: torch.Tensor, base: torch.nn.Module, r: int) -> bool:
+    """Can the kernels of csrc/lora.hip serve ``LoRALinear(base)`` on ``x``?  A
+    GPU and the extension, bf16, a plain ``nn.Linear`` (tensor-parallel linears
+    keep their path), ``r <= 64`` and in/out features that are multiples of 8."""
+    return (x.is_cuda and x.dtype == torch.bfloat16 and type(base) is torch.nn.Linear
+            and base.weight.dtype == torch.bfloat16
+            and _lora_shapes_ok(base.weight.shape[1], base.weight.shape[0], r)
+            and extension_available())
+
+
+class _LoRALinear(torch.autograd.Function):
+    """y = x W^T + bias + scaling (x_lora A^T) B^T over 2-D bf16 inputs with W and
+    bias frozen.  The function owns the base GEMM, so both adapter adds are in
+    place on a tensor nobody else holds: y on the base output, dx on dY W.
+    Saved for the backward: x_lora (x without dropout), T = x_lora A^T [N, r] and
+    the parameters; no [N, O] tensor."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, lora_A, lora_B, scaling, x_lora, ext):
+        y = torch.nn.functional.linear(x, weight, bias)
+        xl = x if x_lora is None else x_lora
+        t = ext.lora_shrink(xl, lora_A, 1.0)
+        ext.lora_expand(y, t, lora_B, scaling, y)
+        ctx.save_for_backward(xl, t, weight, lora_A, lora_B)
+        ctx.scaling, ctx.separate = scaling, x_lora is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        xl, t, weight, lora_A, lora_B = ctx.saved_tensors
+        ext = _require_ext("lora_linear")
+        dy = dy.contiguous()
+        # the kernels read their weight as [cols, inner]: r x O and K x r copies
+        dt = ext.lora_shrink(dy, lora_B.t().contiguous(), ctx.scaling)
+        # dA and dB reduce over N, the library's shape (docs/kernels.md)
+        d_a = dt.t() @ xl if ctx.needs_input_grad[3] else None
+        d_b = (dy.t() @ t).mul_(ctx.scaling) if ctx.needs_input_grad[4] else None
+        dx = dxl = None
+        if ctx.needs_input_grad[0]:
+            dx = dy @ weight
+            if not ctx.separate:
+                ext.lora_expand(dx, dt, lora_A.t().contiguous(), 1.0, dx)
+        if ctx.separate and ctx.needs_input_grad[6]:
+            dxl = dt @ lora_A  # autograd adds it to dx through the dropout
+        return dx, None, None, d_a, d_b, None, dxl, None
+
+
+def lora_linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor],
+                lora_A: torch.Tensor, lora_B: torch.Tensor, scaling: float,
+                x_lora: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A frozen linear with its LoRA adapter:
+    ``x W^T + bias + scaling * (x_lora A^T) B^T`` with ``lora_A`` [r, K],
+    ``lora_B`` [O, r]; ``x_lora`` is the adapter's input where it is not ``x``
+    (the dropout output).
+
+    GPU, bf16, ``r <= 64``, K and O multiples of 8, ``weight`` and ``bias``
+    frozen: the base GEMM stays on the library and the adapter costs two kernels
+    forward (csrc/lora.hip: ``T = x_lora A^T``, then ``y += scaling T B^T`` in
+    place) and two backward (``dT = scaling dY B``, ``dx += dT A`` in place);
+    dA and dB are library GEMMs.  fp32 accumulation, T, dT and every output
+    rounded once.  Anything else, and the CPU: ``reference.lora_linear``."""
+    tensors = [t for t in (x, weight, bias, lora_A, lora_B, x_lora) if t is not None]
+    if (x.is_cuda and all(t.is_cuda and t.dtype == torch.bfloat16 for t in tensors)
+            and not weight.requires_grad and (bias is None or not bias.requires_grad)
+            and weight.dim() == 2 and _lora_shapes_ok(weight.shape[1], weight.shape[0],
+                                                      lora_A.shape[0])
+            and x.numel() > 0):
+        ext = _require_ext("lora_linear")
+        if ext is not None:
+            K = weight.shape[1]
+            y = _LoRALinear.apply(
+                x.reshape(-1, K).contiguous(), weight, bias, lora_A.contiguous(),
+                lora_B.contiguous(), float(scaling),
+                None if x_lora is None else x_lora.reshape(-1, K).contiguous(), ext)
+            return y.view(*x.shape[:-1], weight.shape[0])
+    return reference.lora_linear(x, weight, bias, lora_A, lora_B, scaling, x_lora)
+
+
+# --------------------------------------------------------------------------
 # RoPE
 # --------------------------------------------------------------------------
 

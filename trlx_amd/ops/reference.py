@@ -61,6 +61,18 @@ def gated_act(gate: torch.Tensor, up: Optional[torch.Tensor] = None,
     return fn(gate) * up
 
 
+def lora_linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor],
+                lora_A: torch.Tensor, lora_B: torch.Tensor, scaling: float,
+                x_lora: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``x W^T + bias + scaling * (x_lora A^T) B^T``: a linear with a LoRA adapter,
+    the line ``LoRALinear`` spells out itself when ``ops.lora_enabled()`` is off.
+    ``x_lora`` is the adapter's input where it differs from ``x`` (dropout)."""
+    xa = x if x_lora is None else x_lora
+    lora = torch.nn.functional.linear(
+        torch.nn.functional.linear(xa.to(lora_A.dtype), lora_A), lora_B)
+    return torch.nn.functional.linear(x, weight, bias) + scaling * lora
+
+
 def rope_cos_sin(
     seq_len: int,
     dim: int,
