@@ -97,6 +97,10 @@ at::Tensor lm_logprobs(const at::Tensor& hidden, const at::Tensor& weight,
 void fused_adamw(at::Tensor& p, at::Tensor& master, const at::Tensor& g, at::Tensor& m,
                  at::Tensor& v, long step, double lr, double beta1, double beta2, double eps,
                  double weight_decay, double grad_scale);
+void fused_adamw8(at::Tensor& p, at::Tensor& master, const at::Tensor& g, at::Tensor& m8,
+                  at::Tensor& m_scale, at::Tensor& u8, at::Tensor& u_scale, long step, double lr,
+                  double beta1, double beta2, double eps, double weight_decay, double grad_scale,
+                  long seed, long index_base);
 void stage_gemm(const at::Tensor& a, const at::Tensor& w, const c10::optional<at::Tensor>& bias,
                 at::Tensor& c, const c10::optional<at::Tensor>& nstats,
                 const c10::optional<at::Tensor>& nw, const c10::optional<at::Tensor>& nb,
@@ -203,6 +207,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("v_cache"), py::arg("seq_lens"), py::arg("scale"), py::arg("seq_starts"),
           py::arg("alibi_slopes") = py::none(), py::arg("num_splits") = 0);
   mod.def("fused_adamw", &fused_adamw);
+  // AdamW with e4m3 moment codes + one fp32 scale per 256 elements (adamw8.hip)
+  mod.def("fused_adamw8", &fused_adamw8, py::arg("p"), py::arg("master"), py::arg("g"),
+          py::arg("m8"), py::arg("m_scale"), py::arg("u8"), py::arg("u_scale"), py::arg("step"),
+          py::arg("lr"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"),
+          py::arg("weight_decay"), py::arg("grad_scale"), py::arg("seed"),
+          py::arg("index_base"));
   mod.def("lm_logprobs", &lm_logprobs);
   mod.def("lm_logprobs_v2", &lm_logprobs_v2);
   mod.def("skinny_gemm", &skinny_gemm);

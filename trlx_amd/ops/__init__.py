@@ -500,6 +500,35 @@ def layernorm_add(x: torch.Tensor, res: torch.Tensor, weight: torch.Tensor,
 
 
 # --------------------------------------------------------------------------
+# 8-bit AdamW (csrc/adamw8.hip)
+# --------------------------------------------------------------------------
+
+# Elements per quantization block, elements one 256-thread block of
+# adamw8_kernel owns per trip, and the blocks it launches per CU: an arena of
+# more than CUs * ADAMW8_BLOCKS_PER_CU * ADAMW8_TILE elements takes a second
+# trip of the grid-stride loop.
+ADAMW8_QB = reference.ADAMW8_QB
+ADAMW8_TILE = 2048
+ADAMW8_BLOCKS_PER_CU = 8
+
+
+def adamw8_step(p, master, g, m8, m_scale, u8, u_scale, step, lr, beta1, beta2, eps,
+                weight_decay, grad_scale=1.0, seed=0, index_base=0) -> None:
+    """One AdamW step on a flat arena with e4m3 moment codes and one fp32 scale
+    per 256 elements, in place (format: csrc/adamw8.hip).  On the GPU this is the
+    ``fused_adamw8`` kernel, on CPU tensors ``reference.adamw8_step``."""
+    if p.is_cuda:
+        ext = _require_ext("fused_adamw8")
+        if ext is not None:
+            ext.fused_adamw8(p, master, g, m8, m_scale, u8, u_scale, step, lr, beta1, beta2,
+                             eps, weight_decay, grad_scale, seed, index_base)
+            return
+        raise RuntimeError("adamw8_step has no eager GPU path: build trlx_amd._C")
+    reference.adamw8_step(p, master, g, m8, m_scale, u8, u_scale, step, lr, beta1, beta2, eps,
+                          weight_decay, grad_scale, seed, index_base)
+
+
+# --------------------------------------------------------------------------
 # gated MLP activation (SwiGLU / GeGLU)
 # --------------------------------------------------------------------------
 

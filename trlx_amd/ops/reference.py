@@ -293,6 +293,132 @@ def fused_adamw(
         p.copy_(mp.to(p.dtype))
 
 
+# ---- 8-bit AdamW (csrc/adamw8.hip; the state format is written out there) ----
+
+ADAMW8_QB = 256  # elements per quantization block
+_E4M3_MAX = 448.0
+_U64 = (1 << 64) - 1
+_GOLDEN = 0x9E3779B97F4A7C15
+
+
+def _i64(c: int) -> int:
+    """The int64 with the bits of the uint64 ``c``."""
+    return c - (1 << 64) if c >= 1 << 63 else c
+
+
+def _shr(z: torch.Tensor, k: int) -> torch.Tensor:
+    """Logical right shift of int64 bits."""
+    return (z >> k) & ((1 << (64 - k)) - 1)
+
+
+def _splitmix64(z):
+    """common.h splitmix64 on a python int (mod 2^64) or on int64 tensor bits."""
+    if isinstance(z, int):
+        z = (z + _GOLDEN) & _U64
+        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _U64
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _U64
+        return z ^ (z >> 31)
+    z = z + _i64(_GOLDEN)
+    z = (z ^ _shr(z, 30)) * _i64(0xBF58476D1CE4E5B9)
+    z = (z ^ _shr(z, 27)) * _i64(0x94D049BB133111EB)
+    return z ^ _shr(z, 31)
+
+
+def _f32(x: float) -> float:
+    """``x`` rounded to fp32, as the kernel's float arguments are."""
+    return torch.tensor(x, dtype=torch.float32).item()
+
+
+def _sqrt32(x: torch.Tensor) -> torch.Tensor:
+    """The correctly rounded fp32 square root, as sqrtf on the device is.  The CPU
+    torch.sqrt of a large fp32 tensor is a vector-library call that is 1 ulp
+    off for about 0.7 % of its inputs; rounding the fp64 root is exact (fp64
+    carries more than twice fp32's bits plus two)."""
+    return x.double().sqrt().float()
+
+
+def _per_element(scales: torch.Tensor, n: int) -> torch.Tensor:
+    return scales.repeat_interleave(ADAMW8_QB)[:n]
+
+
+def adamw8_dequant(codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """fp32 moments of e4m3 ``codes`` uint8 [n] and ``scales`` fp32 [ceil(n/256)]."""
+    return codes.view(torch.float8_e4m3fn).float() * _per_element(scales, codes.numel())
+
+
+def _adamw8_scales(x: torch.Tensor) -> torch.Tensor:
+    """absmax of every 256-element block (a short tail block: of its real
+    elements) times 1/448."""
+    n = x.numel()
+    nb = -(-n // ADAMW8_QB)
+    padded = torch.zeros(nb * ADAMW8_QB, dtype=torch.float32, device=x.device)
+    padded[:n] = x.abs()
+    return padded.view(nb, ADAMW8_QB).amax(dim=1) * _f32(1.0 / _E4M3_MAX)
+
+
+def _scaled(x: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """x / scale clamped to +-448; 0 in a block whose scale is 0."""
+    s = _per_element(scales, x.numel())
+    y = torch.where(s > 0, x / torch.where(s > 0, s, torch.ones_like(s)), torch.zeros_like(x))
+    return y.clamp(-_E4M3_MAX, _E4M3_MAX)
+
+
+def adamw8_stochastic_round(y: torch.Tensor, idx: torch.Tensor, seed: int,
+                            step: int) -> torch.Tensor:
+    """fp32 ``y`` in [0, 448] rounded down or up to the e4m3 grid, up with the
+    probability of its fraction: e = max(floor(log2 y), -6), grid step 2^(e-3),
+    q = min(floor(y / step + r) * step, 448) with r = (h >> 40) 2^-24 and
+    h = splitmix64(key ^ splitmix64(idx)), key = splitmix64(seed ^ golden * step).
+    ``idx`` int64: the elements' indices in the unsharded arena.  The min: the
+    fp32 sum y / step + r can round up past a y on the grid (r within 2^-21 of
+    1), and from 448, every block's absmax, the next step is 480, which e4m3
+    does not have and would store as NaN."""
+    key = _splitmix64((seed ^ (_GOLDEN * step)) & _U64)
+    h = _splitmix64(_splitmix64(idx) ^ _i64(key))
+    r = _shr(h, 40).float() * 2.0 ** -24
+    e = (((y.view(torch.int32) >> 23) & 0xFF) - 127).clamp(min=-6)
+    inv_step = ((130 - e) << 23).view(torch.float32)
+    grid = ((124 + e) << 23).view(torch.float32)
+    return (torch.floor(y * inv_step + r) * grid).clamp(max=_E4M3_MAX)
+
+
+def adamw8_step(p, master, g, m8, m_scale, u8, u_scale, step: int, lr: float, beta1: float,
+                beta2: float, eps: float, weight_decay: float, grad_scale: float = 1.0,
+                seed: int = 0, index_base: int = 0) -> None:
+    """One AdamW step on a flat arena with 8-bit moment state, in place: the CPU
+    path of ``FusedAdamW8bit`` and the bit-level definition ``fused_adamw8`` is
+    tested against.  m = e4m3(m8) * m_scale[block], u = sqrt(v) = e4m3(u8) *
+    u_scale[block], one fp32 scale = absmax / 448 per 256 elements; m is encoded
+    round-to-nearest-even, u by ``adamw8_stochastic_round``.  Every operation is
+    one fp32 rounding, in the order of the kernel (no fused multiply-add)."""
+    n = p.numel()
+    lr, b1, b2, eps = _f32(lr), _f32(beta1), _f32(beta2), _f32(eps)
+    omb1, omb2 = _f32(1.0 - b1), _f32(1.0 - b2)  # fp32 subtractions: exact in double
+    lrwd = _f32(lr * _f32(weight_decay))
+    # divisors as tensors: a tensor / python-scalar may multiply by the reciprocal
+    bc1 = torch.full((n,), 1.0 - beta1 ** step, dtype=torch.float32)
+    bc2 = torch.full((n,), 1.0 - beta2 ** step, dtype=torch.float32)
+
+    gf = g.float() * _f32(grad_scale)
+    u = adamw8_dequant(u8, u_scale)
+    m = b1 * adamw8_dequant(m8, m_scale) + omb1 * gf
+    v = b2 * (u * u) + omb2 * (gf * gf)
+    w = master - lrwd * master
+    w = w - (lr * (m / bc1)) / (_sqrt32(v / bc2) + eps)
+    un = _sqrt32(v)
+
+    new_ms, new_us = _adamw8_scales(m), _adamw8_scales(un)
+    idx = torch.arange(index_base, index_base + n, dtype=torch.int64)
+    q = adamw8_stochastic_round(_scaled(un, new_us), idx, seed, step)
+    m8.copy_(_scaled(m, new_ms).to(torch.float8_e4m3fn).view(torch.uint8))
+    u8.copy_(q.to(torch.float8_e4m3fn).view(torch.uint8))
+    m_scale.copy_(new_ms)
+    u_scale.copy_(new_us)
+    master.copy_(w)
+    if not (p.dtype == torch.float32 and p.data_ptr() == master.data_ptr()):
+        p.copy_(w.to(p.dtype))
+
+
 def flash_prefill(q, k, v, key_starts=None, start_pos: int = 0, scale: float = 1.0, tk=None,
                   alibi_slopes=None):
     """fp32 reference for the flash prefill kernel (masking semantics match

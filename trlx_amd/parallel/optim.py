@@ -82,13 +82,15 @@ class FusedAdamW(torch.optim.Optimizer):
                 master = p_shard.float() if (dtype != torch.float32 or self.zero) else flat_p
                 if self.zero and dtype == torch.float32:
                     master = p_shard.clone()
-                m = torch.zeros_like(master)
-                v = torch.zeros_like(master)
                 group_arenas.append(dict(
-                    params=plist, flat_p=flat_p, flat_g=flat_g, master=master, m=m, v=v,
-                    offsets=offsets, shard=shard, lo=lo,
+                    params=plist, flat_p=flat_p, flat_g=flat_g, master=master,
+                    offsets=offsets, shard=shard, lo=lo, **self._new_moments(master),
                 ))
             self._arenas.append(group_arenas)
+
+    def _new_moments(self, master: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """The zeroed moment state of one arena (or ZeRO shard)."""
+        return dict(m=torch.zeros_like(master), v=torch.zeros_like(master))
 
     # --- optimizer protocol -------------------------------------------------
 
@@ -113,12 +115,7 @@ class FusedAdamW(torch.optim.Optimizer):
                     g_sh = arena["flat_g"][lo : lo + shard]
                 else:
                     p_sh, g_sh = arena["flat_p"], arena["flat_g"]
-                if arena["flat_p"].is_cuda:
-                    ext = ops._require_ext("fused_adamw")
-                    ext.fused_adamw(p_sh, arena["master"], g_sh, arena["m"], arena["v"],
-                                    self._step, lr, beta1, beta2, eps, wd, self.grad_scale)
-                else:
-                    self._cpu_step_flat(p_sh, g_sh, arena, lr, beta1, beta2, eps, wd)
+                self._step_arena(arena, p_sh, g_sh, lr, beta1, beta2, eps, wd)
                 if self.zero:
                     if dist.get_backend(self.zero_group) == "gloo":
                         chunks = list(arena["flat_p"].chunk(self._zero_world))
@@ -126,6 +123,14 @@ class FusedAdamW(torch.optim.Optimizer):
                     else:
                         dist.all_gather_into_tensor(arena["flat_p"], p_sh, group=self.zero_group)
         return loss
+
+    def _step_arena(self, arena, p_sh, g_sh, lr, beta1, beta2, eps, wd):
+        if arena["flat_p"].is_cuda:
+            ext = ops._require_ext("fused_adamw")
+            ext.fused_adamw(p_sh, arena["master"], g_sh, arena["m"], arena["v"],
+                            self._step, lr, beta1, beta2, eps, wd, self.grad_scale)
+        else:
+            self._cpu_step_flat(p_sh, g_sh, arena, lr, beta1, beta2, eps, wd)
 
     def _cpu_step_flat(self, p_flat, g_flat, arena, lr, beta1, beta2, eps, wd):
         g = g_flat.float() * self.grad_scale
@@ -148,6 +153,12 @@ class FusedAdamW(torch.optim.Optimizer):
 
     # --- persistence ----------------------------------------------------------
 
+    state_bits = 32  # width of the moment state; load_state_dict refuses another
+
+    def _state_keys(self, arena) -> Tuple[str, ...]:
+        """The tensors of one arena that make up its optimizer state."""
+        return ("master", "m", "v")
+
     def state_dict(self):
         return {
             "step": self._step,
@@ -156,21 +167,31 @@ class FusedAdamW(torch.optim.Optimizer):
                 {k: v for k, v in g.items() if k != "params"} for g in self.param_groups
             ],
             "arenas": [
-                [{"master": a["master"], "m": a["m"], "v": a["v"]} for a in group_arenas]
+                [{k: a[k] for k in self._state_keys(a)} for a in group_arenas]
                 for group_arenas in self._arenas
             ],
         }
 
     def load_state_dict(self, state):
+        bits = state.get("state_bits", 32)
+        if bits != self.state_bits:
+            raise ValueError(
+                f"{type(self).__name__} keeps {self.state_bits}-bit moment state but the state "
+                f"to load is {bits}-bit: load it with the optimizer that saved it")
         self._step = state["step"]
         self.grad_scale = state.get("grad_scale", self.grad_scale)
         for g, sg in zip(self.param_groups, state["param_groups"]):
             g.update(sg)
         for group_arenas, sga in zip(self._arenas, state["arenas"]):
             for arena, sa in zip(group_arenas, sga):
-                arena["master"].copy_(sa["master"].to(arena["master"].device))
-                arena["m"].copy_(sa["m"].to(arena["m"].device))
-                arena["v"].copy_(sa["v"].to(arena["v"].device))
+                keys = self._state_keys(arena)
+                if set(sa) != set(keys):
+                    raise ValueError(
+                        f"{type(self).__name__}.load_state_dict: an arena of "
+                        f"{arena['master'].numel()} elements keeps {sorted(keys)} but the "
+                        f"state has {sorted(sa)}")
+                for k in keys:
+                    arena[k].copy_(sa[k].to(arena[k].device))
                 if arena["flat_p"].dtype != torch.float32:
                     arena["flat_p"].copy_(arena["master"].to(arena["flat_p"].dtype))
 
@@ -184,6 +205,60 @@ class FusedAdamW(torch.optim.Optimizer):
                 entries = [(p, off, n) for p, (off, n) in zip(arena["params"], arena["offsets"])]
                 out.append((arena["flat_g"], entries))
         return out
+
+
+class FusedAdamW8bit(FusedAdamW):
+    """``FusedAdamW`` with 8-bit moment state: per arena (per shard under ZeRO)
+    the fp32 ``m`` / ``v`` become e4m3 codes ``m8`` / ``u8`` (u = sqrt(v)) with
+    one fp32 scale per 256 elements, 6 + 1/32 B of state per parameter instead
+    of 12 (format: csrc/adamw8.hip).  Arenas, masters, ZeRO and ``grad_arenas``
+    are the parent's.  An arena (shard) of fewer than ``min_8bit_size`` elements
+    keeps fp32 moments and the parent's kernel.  ``seed`` keys the stochastic
+    rounding of ``u``; the draws depend on (seed, step, element index in the
+    unsharded arena) only, so a sharded and an unsharded run round alike.
+
+    On GPU the step is the trlx_amd._C.fused_adamw8 kernel, on CPU
+    ``reference.adamw8_step``, which defines it bit for bit."""
+
+    state_bits = 8
+
+    def __init__(self, params: Iterable[torch.nn.Parameter], lr: float = 1e-3,
+                 betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 0.0, grad_scale: float = 1.0,
+                 zero: bool = False, zero_group=None, min_8bit_size: int = 4096,
+                 seed: int = 0):
+        self.min_8bit_size = int(min_8bit_size)
+        self.seed = int(seed)
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                         grad_scale=grad_scale, zero=zero, zero_group=zero_group)
+
+    def _new_moments(self, master: torch.Tensor) -> Dict[str, torch.Tensor]:
+        n = master.numel()
+        if n < self.min_8bit_size:
+            return super()._new_moments(master)
+        nb = -(-n // ops.ADAMW8_QB)
+        codes = dict(device=master.device, dtype=torch.uint8)
+        scales = dict(device=master.device, dtype=torch.float32)
+        return dict(m8=torch.zeros(n, **codes), m_scale=torch.zeros(nb, **scales),
+                    u8=torch.zeros(n, **codes), u_scale=torch.zeros(nb, **scales))
+
+    def _step_arena(self, arena, p_sh, g_sh, lr, beta1, beta2, eps, wd):
+        if "m8" not in arena:
+            return super()._step_arena(arena, p_sh, g_sh, lr, beta1, beta2, eps, wd)
+        ops.adamw8_step(p_sh, arena["master"], g_sh, arena["m8"], arena["m_scale"], arena["u8"],
+                        arena["u_scale"], self._step, lr, beta1, beta2, eps, wd,
+                        self.grad_scale, self.seed, arena["lo"] if self.zero else 0)
+
+    def _state_keys(self, arena) -> Tuple[str, ...]:
+        return ("master", "m8", "m_scale", "u8", "u_scale") if "m8" in arena \
+            else super()._state_keys(arena)
+
+    def state_dict(self):
+        return dict(super().state_dict(), state_bits=self.state_bits, seed=self.seed)
+
+    def load_state_dict(self, state):
+        super().load_state_dict(state)
+        self.seed = state.get("seed", self.seed)
 
 
 class NullOptimizer:
@@ -236,6 +311,16 @@ def build_optimizer(model: torch.nn.Module, name: str, kwargs: dict, world: int 
 
         return FusedAdamW(params, grad_scale=1.0 / world, zero=zero,
                           zero_group=topo.dp_group(), **kwargs)
+    if name in ("adamw_8bit", "adamw_8bit_bnb", "adam_8bit_bnb"):
+        from . import topo
+
+        if name == "adam_8bit_bnb" and kwargs.get("weight_decay", 0.0) != 0:
+            raise ValueError(
+                "adam_8bit_bnb is served by the 8-bit AdamW, which equals Adam only at "
+                f"weight_decay == 0 (got {kwargs['weight_decay']}): set it to 0 or name "
+                "adamw_8bit_bnb for decoupled weight decay")
+        return FusedAdamW8bit(params, grad_scale=1.0 / world, zero=zero,
+                              zero_group=topo.dp_group(), **kwargs)
     if name == "adam":
         return torch.optim.Adam(params, **kwargs)
     if name == "sgd":

@@ -66,6 +66,11 @@ class OptimizerName(str, Enum):
     ADAMW = "adamw"
     FUSED_ADAMW = "fused_adamw"  # native arena AdamW (HIP multi-tensor kernel)
     SGD = "sgd"
+    # native 8-bit AdamW (e4m3 moment codes, csrc/adamw8.hip) and the reference's
+    # bitsandbytes names for it; adam_8bit_bnb only with weight_decay == 0
+    ADAMW_8BIT = "adamw_8bit"
+    ADAMW_8BIT_BNB = "adamw_8bit_bnb"
+    ADAM_8BIT_BNB = "adam_8bit_bnb"
 
 
 def get_optimizer_class(name) -> type:
@@ -74,7 +79,8 @@ def get_optimizer_class(name) -> type:
     name = OptimizerName(name) if not isinstance(name, OptimizerName) else name
     if name == OptimizerName.ADAM:
         return torch.optim.Adam
-    if name in (OptimizerName.ADAMW, OptimizerName.FUSED_ADAMW):
+    if name in (OptimizerName.ADAMW, OptimizerName.FUSED_ADAMW, OptimizerName.ADAMW_8BIT,
+                OptimizerName.ADAMW_8BIT_BNB, OptimizerName.ADAM_8BIT_BNB):
         return torch.optim.AdamW
     if name == OptimizerName.SGD:
         return torch.optim.SGD
