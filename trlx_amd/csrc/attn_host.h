@@ -16,8 +16,8 @@
 
 // The head dims each kernel family is instantiated for: the one place on the
 // C++ side.  ops/__init__.py mirrors them as FLASH_HEAD_DIMS,
-// SEQ2SEQ_FLASH_HEAD_DIMS, DECODE_HEAD_DIMS, SEQ2SEQ_DECODE_HEAD_DIMS and
-// GQA_DECODE_HEAD_DIMS.
+// SEQ2SEQ_FLASH_HEAD_DIMS, DECODE_HEAD_DIMS, SEQ2SEQ_DECODE_HEAD_DIMS,
+// GQA_DECODE_HEAD_DIMS and KV_FP8_HEAD_DIMS.
 template <int... Ds>
 struct HeadDims {};
 constexpr HeadDims<64, 96, 128, 256> kFlashHeadDims{};       // flash fwd + bwd
@@ -25,6 +25,7 @@ constexpr HeadDims<64, 128> kSeq2SeqFlashHeadDims{};         // their seq2seq mo
 constexpr HeadDims<32, 64, 96, 128, 256> kDecodeHeadDims{};  // attention_decode, fused
 constexpr HeadDims<64, 128> kSeq2SeqDecodeHeadDims{};        // s2s_decode.hip (T5 per-token step)
 constexpr HeadDims<64, 128> kGqaDecodeHeadDims{};            // attn_decode_gqa.hip (group per block)
+constexpr HeadDims<64, 128> kKvFp8HeadDims{};  // kv_fp8.hip, attn_decode_fp8.hip (fp8 KV cache)
 
 // ---- runtime value -> compile-time constant ------------------------------------
 

@@ -63,6 +63,14 @@ at::Tensor attention_decode_gqa(const at::Tensor& q, const at::Tensor& kc, const
                                 const at::Tensor& seq_lens, double scale,
                                 const c10::optional<at::Tensor>& seq_starts,
                                 const c10::optional<at::Tensor>& alibi_slopes, long num_splits);
+void kv_store_fp8(const at::Tensor& k, const at::Tensor& v, at::Tensor& k8, at::Tensor& k_scale,
+                  at::Tensor& v8, at::Tensor& v_scale,
+                  const c10::optional<at::Tensor>& start_dev, long start_host);
+at::Tensor attention_decode_fp8(const at::Tensor& q, const at::Tensor& k8,
+                                const at::Tensor& k_scale, const at::Tensor& v8,
+                                const at::Tensor& v_scale, const at::Tensor& seq_lens,
+                                double scale, const c10::optional<at::Tensor>& seq_starts,
+                                const c10::optional<at::Tensor>& alibi_slopes, long num_splits);
 at::Tensor lm_logprobs_v2(const at::Tensor& hidden, const at::Tensor& weight,
                           const at::Tensor& labels);
 at::Tensor skinny_gemm(const at::Tensor& a, const at::Tensor& w,
@@ -206,6 +214,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("attention_decode_gqa", &attention_decode_gqa, py::arg("q"), py::arg("k_cache"),
           py::arg("v_cache"), py::arg("seq_lens"), py::arg("scale"), py::arg("seq_starts"),
           py::arg("alibi_slopes") = py::none(), py::arg("num_splits") = 0);
+  // fp8 KV cache: e4m3 codes + one fp32 scale per key (kv_fp8.hip, attn_decode_fp8.hip)
+  mod.def("kv_store_fp8", &kv_store_fp8, py::arg("k"), py::arg("v"), py::arg("k8"),
+          py::arg("k_scale"), py::arg("v8"), py::arg("v_scale"), py::arg("start_dev"),
+          py::arg("start_host"));
+  mod.def("attention_decode_fp8", &attention_decode_fp8, py::arg("q"), py::arg("k8"),
+          py::arg("k_scale"), py::arg("v8"), py::arg("v_scale"), py::arg("seq_lens"),
+          py::arg("scale"), py::arg("seq_starts"), py::arg("alibi_slopes") = py::none(),
+          py::arg("num_splits") = 0);
   mod.def("fused_adamw", &fused_adamw);
   // AdamW with e4m3 moment codes + one fp32 scale per 256 elements (adamw8.hip)
   mod.def("fused_adamw8", &fused_adamw8, py::arg("p"), py::arg("master"), py::arg("g"),

@@ -194,7 +194,9 @@ class DecodeEngine:
         self.gen = gen
         self.device = device
         self.seed = gen.seed if gen.seed is not None else int(torch.randint(0, 2**31 - 1, (1,)).item())
-        self.kv = model.new_kv_cache(batch, cache_len, device=device)
+        # TRLX_AMD_FP8_KV=1: e4m3 codes + per-key scales; the step stays one graph
+        self.kv = model.new_kv_cache(batch, cache_len, device=device,
+                                     kv_dtype=model.generation_kv_dtype(device))
         # fused stage-kernel step (5 kernels/layer): eligible archs only, and
         # only for the plain sampler the lm_sample kernel implements.
         # OPT-IN (TRLX_AMD_FUSED_DECODE=1): the same-box A/B currently favors
@@ -652,7 +654,8 @@ def _generate_eager(model, input_ids, attention_mask, gen: GenerateConfig, shapi
     device = input_ids.device
     nv = getattr(model, "num_virtual_tokens", 0)
     key_starts = (T - attention_mask.sum(-1)).to(torch.int32)
-    kv = model.new_kv_cache(B, T + nv + gen.max_new_tokens, device=device)
+    kv = model.new_kv_cache(B, T + nv + gen.max_new_tokens, device=device,
+                            kv_dtype=model.generation_kv_dtype(device))
 
     out = model(input_ids, attention_mask=attention_mask, kv_cache=kv, start_pos=0,
                 return_logits=False)

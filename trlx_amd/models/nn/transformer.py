@@ -19,6 +19,7 @@ Design points:
 """
 
 import math
+import os
 from dataclasses import dataclass
 from typing import List, Optional, Tuple
 
@@ -115,7 +116,21 @@ class KVCache:
     """Preallocated contiguous KV cache sized for HBM3E residency."""
 
     def __init__(self, num_layers: int, batch: int, num_kv_heads: int, max_len: int, head_dim: int,
-                 device, dtype):
+                 device, dtype, kv_dtype: Optional[str] = None):
+        self.max_len = max_len
+        self.cur_len = 0
+        self.fp8 = kv_dtype == "fp8"
+        if self.fp8:
+            # e4m3 codes + one fp32 scale per (row, KV head, key): written by
+            # ops.kv_store_fp8, read by the fp8 form of ops.attention_decode.
+            # Zero-init: code 0 is +0.0 and scale 0 dequantizes to 0
+            shape = (batch, num_kv_heads, max_len, head_dim)
+            self.k, self.v, self.k_scale, self.v_scale = (
+                [torch.zeros(s, device=device, dtype=t) for _ in range(num_layers)]
+                for s, t in ((shape, torch.uint8), (shape, torch.uint8),
+                             (shape[:3], torch.float32), (shape[:3], torch.float32)))
+            return
+        assert kv_dtype is None, f"unknown kv_dtype {kv_dtype!r}"
         # zero-init: unwritten slots must be finite (masked-out positions can
         # still flow through 0*x products in the eager reference path)
         self.k = [
@@ -126,8 +141,12 @@ class KVCache:
             torch.zeros(batch, num_kv_heads, max_len, head_dim, device=device, dtype=dtype)
             for _ in range(num_layers)
         ]
-        self.max_len = max_len
-        self.cur_len = 0
+
+    def store_fp8(self, layer: int, k: torch.Tensor, v: torch.Tensor, start) -> None:
+        """Quantize k, v [B, Hkv, T, D] into the fp8 cache at ``start + t``
+        (``start``: host int or the device cache index)."""
+        ops.kv_store_fp8(k, v, self.k[layer], self.k_scale[layer], self.v[layer],
+                         self.v_scale[layer], start)
 
     def update(self, layer: int, k: torch.Tensor, v: torch.Tensor, start: int) -> Tuple[torch.Tensor, torch.Tensor]:
         T = k.shape[2]
@@ -181,9 +200,21 @@ class Attention(nn.Module):
         def project(out):  # attention output [B, H, T, D] -> o_proj of [B, T, H*D]
             return dense(self.o_proj, out.transpose(1, 2).reshape(B, T, -1))
 
+        # fp8 KV cache (KVCache(kv_dtype="fp8")): the decode step is qkv_prep ->
+        # kv_store_fp8 -> attention_decode on the codes, below; what it does
+        # not cover stays on bf16 caches
+        fp8_cache = kv_cache is not None and getattr(kv_cache, "fp8", False)
+        fp8_decode = fp8_cache and T == 1 and ctx.seq_lens is not None
+        if fp8_cache and (ctx.prefix_kv is not None or ctx.cache_rows is not None
+                          or (not fp8_decode and ctx.start_pos > 0)):
+            raise NotImplementedError(
+                "the fp8 KV cache serves a prefill from position 0 and single-token decode "
+                "steps; prefix tuning, per-row cache positions (continuous batching) and "
+                "chunked prefill need a bf16 KVCache")
+
         # fused single-token decode path: decode_prep (split+RoPE+cache
         # append) + flash-decode attention, fully device-side (hipGraph-safe)
-        if (T == 1 and kv_cache is not None and ctx.cache_idx is not None
+        if (T == 1 and kv_cache is not None and ctx.cache_idx is not None and not fp8_cache
                 and ctx.seq_lens is not None and x.is_cuda
                 and self.head_dim in ops.DECODE_HEAD_DIMS):
             # (unsupported head dims fall through to the eager T=1 math below)
@@ -241,6 +272,21 @@ class Attention(nn.Module):
             idx = ctx.virtual_slots.view(B_, 1, n_, 1).expand(B_, k.shape[1], n_, k.shape[3])
             k = k.scatter(2, idx, pk.unsqueeze(0).expand(B_, -1, -1, -1))
             v = v.scatter(2, idx, pv.unsqueeze(0).expand(B_, -1, -1, -1))
+
+        if fp8_cache:
+            # k is unscaled (qkv_prep scales q only), as the bf16 cache stores it
+            start = ctx.cache_idx if fp8_decode and ctx.cache_idx is not None else ctx.start_pos
+            kv_cache.store_fp8(self.layer_idx, k, v, start)
+            if fp8_decode:
+                out = ops.attention_decode(
+                    q, kv_cache.k[self.layer_idx], kv_cache.v[self.layer_idx], ctx.seq_lens,
+                    1.0 if pre_scaled else self.scale, seq_starts=ctx.key_starts,
+                    alibi_slopes=ctx.alibi_slopes, k_scale=kv_cache.k_scale[self.layer_idx],
+                    v_scale=kv_cache.v_scale[self.layer_idx])
+                return project(out)
+            # prefill: attention runs on the bf16 k, v just computed, through
+            # the no-cache branches below
+            kv_cache = None
 
         # what both flash directions need; each adds its grad mode and gate
         flash_common = (
@@ -740,11 +786,30 @@ class CausalTransformer(nn.Module):
             logits = self.lm_head(hs)
         return TransformerOutput(logits=logits, last_hidden_state=h, hidden_at_layer=hidden_at)
 
-    def new_kv_cache(self, batch: int, max_len: int, device=None, dtype=None) -> KVCache:
+    def new_kv_cache(self, batch: int, max_len: int, device=None, dtype=None,
+                     kv_dtype: Optional[str] = None) -> KVCache:
         p = next(self.parameters())
         kv_heads_local = self.config.num_kv_heads // topo.tp_size()
         return KVCache(len(self.layers), batch, kv_heads_local, max_len,
-                       self.config.head_dim, device or p.device, dtype or p.dtype)
+                       self.config.head_dim, device or p.device, dtype or p.dtype,
+                       kv_dtype=kv_dtype)
+
+    def generation_kv_dtype(self, device=None) -> Optional[str]:
+        """``"fp8"`` when generation should keep its KV cache as e4m3 codes
+        (``ops.kv_fp8_enabled``: opt-in by TRLX_AMD_FP8_KV=1) and this model
+        can: bf16 weights on the GPU.  What the fp8 cache does not serve
+        raises instead of quietly keeping bf16."""
+        p = next(self.parameters())
+        device = torch.device(device) if device is not None else p.device
+        if not (ops.kv_fp8_enabled(self.config.head_dim) and device.type == "cuda"
+                and p.dtype == torch.bfloat16):
+            return None
+        if self.prefix_kv is not None:
+            raise NotImplementedError("TRLX_AMD_FP8_KV=1: prefix tuning needs a bf16 KV cache")
+        if os.environ.get("TRLX_AMD_FUSED_DECODE") == "1":
+            raise NotImplementedError(
+                "TRLX_AMD_FP8_KV=1: the TRLX_AMD_FUSED_DECODE stage kernels read a bf16 KV cache")
+        return "fp8"
 
     def num_parameters(self) -> int:
         return sum(p.numel() for p in self.parameters())

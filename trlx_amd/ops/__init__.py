@@ -51,6 +51,10 @@ SEQ2SEQ_DECODE_HEAD_DIMS = (64, 128)
 # attn_host.h): one block per KV head and chunk of 16 query heads.
 GQA_DECODE_HEAD_DIMS = (64, 128)
 
+# fp8 KV cache (csrc/kv_fp8.hip, csrc/attn_decode_fp8.hip; kKvFp8HeadDims in
+# attn_host.h): e4m3 codes and one fp32 scale per (batch row, KV head, key).
+KV_FP8_HEAD_DIMS = (64, 128)
+
 
 def _flash_gate(head_dim: int, train: bool, built, prefill_default, train_default) -> bool:
     """The gate behind ``flash_enabled`` / ``seq2seq_flash_enabled``: ``built``
@@ -106,6 +110,16 @@ def gqa_decode_enabled(head_dim: int, group: int) -> bool:
     loaded, ``group >= 2`` and a head dim in ``GQA_DECODE_HEAD_DIMS``."""
     return (os.environ.get("TRLX_AMD_GQA_DECODE") == "1" and group >= 2
             and head_dim in GQA_DECODE_HEAD_DIMS and extension_available())
+
+
+def kv_fp8_enabled(head_dim: int) -> bool:
+    """Does generation keep its KV cache as e4m3 codes with one fp32 scale per
+    key (``KVCache(kv_dtype="fp8")``, ``kv_store_fp8``, the fp8 form of
+    ``attention_decode``)?  OPT-IN until its end-to-end A/B exists
+    (profiles/kv_fp8_notes.md): ``TRLX_AMD_FP8_KV=1``, the extension loaded and
+    a head dim in ``KV_FP8_HEAD_DIMS``."""
+    return (os.environ.get("TRLX_AMD_FP8_KV") == "1" and head_dim in KV_FP8_HEAD_DIMS
+            and extension_available())
 
 
 _EXT = None
@@ -1094,6 +1108,8 @@ def attention_decode(
     alibi_slopes: Optional[torch.Tensor] = None,
     grouped: Optional[bool] = None,
     num_splits: int = 0,
+    k_scale: Optional[torch.Tensor] = None,
+    v_scale: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
     """Fused decode attention: q [B, Hq, 1, D] vs cache [B, Hkv, S, D]
     with per-row valid key range [seq_starts[b], seq_lens[b]) -> [B, Hq, 1, D]
@@ -1111,11 +1127,32 @@ def attention_decode(
     else raises), ``None`` follows ``gqa_decode_enabled``.  ``num_splits`` is
     that kernel's number of key splits: 0 lets it choose from the static
     sizes, a positive value forces it.  On CPU both are ignored.
+
+    fp8 cache: ``uint8`` caches (e4m3 codes, the format ``kv_store_fp8``
+    writes) with ``k_scale`` / ``v_scale`` fp32 [B, Hkv, S] take
+    csrc/attn_decode_fp8.hip on the GPU: bf16 q, any Hq / Hkv >= 1, D in
+    ``KV_FP8_HEAD_DIMS``; it honours ``num_splits`` and ignores ``grouped``.
+    On CPU the cache is dequantized and the reference body below runs.
     """
+    fp8 = k_cache.dtype == torch.uint8 or v_cache.dtype == torch.uint8
+    if fp8 or k_scale is not None or v_scale is not None:
+        if not (k_cache.dtype == torch.uint8 and v_cache.dtype == torch.uint8
+                and k_scale is not None and v_scale is not None):
+            raise ValueError("attention_decode: an fp8 KV cache is two uint8 code tensors "
+                             "with both k_scale and v_scale; other caches take neither")
+        if q.is_cuda and q.dtype != torch.bfloat16:
+            raise ValueError(f"attention_decode: the fp8 KV cache kernel needs bf16 q, got {q.dtype}")
     if q.is_cuda:
         ext = _require_ext("attention_decode")
         if ext is not None:
             ss = None if seq_starts is None else seq_starts.to(torch.int32).contiguous()
+            if fp8:
+                return ext.attention_decode_fp8(
+                    q.contiguous(), k_cache.contiguous(), k_scale.contiguous(),
+                    v_cache.contiguous(), v_scale.contiguous(),
+                    seq_lens.to(torch.int32).contiguous(), scale, ss, alibi_slopes,
+                    int(num_splits),
+                )
             if grouped is None:
                 grouped = gqa_decode_enabled(q.shape[-1], q.shape[1] // k_cache.shape[1])
             if grouped:
@@ -1133,8 +1170,12 @@ def attention_decode(
     Hkv = k_cache.shape[1]
     S = k_cache.shape[2]
     qf = q.float()
-    kf = k_cache.float()
-    vf = v_cache.float()
+    if fp8:
+        kf = reference.kv_dequantize_fp8(k_cache, k_scale)
+        vf = reference.kv_dequantize_fp8(v_cache, v_scale)
+    else:
+        kf = k_cache.float()
+        vf = v_cache.float()
     if Hkv != Hq:
         rep = Hq // Hkv
         kf = kf.repeat_interleave(rep, dim=1)
@@ -1150,6 +1191,32 @@ def attention_decode(
     scores = scores.masked_fill(mask, float("-inf"))
     probs = torch.softmax(scores, dim=-1)
     return torch.matmul(probs, vf).to(q.dtype)
+
+
+def kv_store_fp8(k: torch.Tensor, v: torch.Tensor, k8: torch.Tensor, k_scale: torch.Tensor,
+                 v8: torch.Tensor, v_scale: torch.Tensor, start) -> None:
+    """Quantize new K and V rows ``[B, Hkv, T, D]`` into an fp8 KV cache, in
+    place: ``k8`` / ``v8`` uint8 ``[B, Hkv, S, D]`` e4m3 codes, ``k_scale`` /
+    ``v_scale`` fp32 ``[B, Hkv, S]`` (format and bit-level definition:
+    ``reference.kv_quantize_fp8``).  Token ``t`` goes to cache position
+    ``start + t``, clamped into the cache; ``start`` is a python int (prefill),
+    a one-element device tensor (the captured decode step's ``cache_idx``) or
+    one position per batch row ``[B]``.  On the GPU one launch of
+    csrc/kv_fp8.hip handles K and V and reads them through their strides (bf16,
+    unit stride over D, D in ``KV_FP8_HEAD_DIMS``); on CPU tensors the reference."""
+    if k.is_cuda:
+        ext = _require_ext("kv_store_fp8")
+        if ext is not None:
+            if k.dtype != torch.bfloat16 or v.dtype != torch.bfloat16:
+                raise ValueError(f"kv_store_fp8: k and v must be bf16, got {k.dtype} / {v.dtype}")
+            if torch.is_tensor(start):
+                ext.kv_store_fp8(k, v, k8, k_scale, v8, v_scale,
+                                 start.reshape(-1).to(torch.int64), 0)
+            else:
+                ext.kv_store_fp8(k, v, k8, k_scale, v8, v_scale, None, int(start))
+            return
+        raise RuntimeError("kv_store_fp8 has no eager GPU path: build trlx_amd._C")
+    reference.kv_store_fp8(k, v, k8, k_scale, v8, v_scale, start)
 
 
 # --------------------------------------------------------------------------

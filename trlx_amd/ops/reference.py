@@ -419,6 +419,44 @@ def adamw8_step(p, master, g, m8, m_scale, u8, u_scale, step: int, lr: float, be
         p.copy_(w.to(p.dtype))
 
 
+def kv_quantize_fp8(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The fp8 KV-cache format, bit for bit (csrc/kv_fp8.hip reproduces every
+    code and scale): rows ``x[..., D]`` -> e4m3 ``codes`` uint8 ``[..., D]`` and
+    one fp32 ``scale [...]`` per row.  scale = absmax / 448 (one fp32 division),
+    code = round-to-nearest-even of x / scale clamped to +-448, so no NaN code
+    (0x7F / 0xFF) is ever produced; an all-zero row has scale 0 and codes 0."""
+    xf = x.float()
+    amax = xf.abs().amax(dim=-1, keepdim=True)
+    # divisor as a tensor: a tensor / python-scalar may multiply by the reciprocal
+    scale = amax / torch.full_like(amax, _E4M3_MAX)
+    live = scale > 0
+    y = torch.where(live, xf / torch.where(live, scale, torch.ones_like(scale)),
+                    torch.zeros_like(xf)).clamp(-_E4M3_MAX, _E4M3_MAX)
+    return y.to(torch.float8_e4m3fn).view(torch.uint8), scale.squeeze(-1)
+
+
+def kv_dequantize_fp8(codes: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """fp32 rows of ``kv_quantize_fp8``'s output: e4m3(code) * scale."""
+    return codes.view(torch.float8_e4m3fn).float() * scale.unsqueeze(-1)
+
+
+def kv_store_fp8(k, v, k8, k_scale, v8, v_scale, start) -> None:
+    """Quantize k, v ``[B, Hkv, T, D]`` into the fp8 cache at positions
+    ``start + t`` (clamped into the cache): ``start`` an int, a one-element
+    tensor, or one position per batch row ``[B]``."""
+    B, _, T, _ = k.shape
+    S = k8.shape[2]
+    if not torch.is_tensor(start):
+        start = torch.tensor([int(start)])
+    rows = start.reshape(-1).long().to(k8.device).expand(B)
+    pos = (rows.view(B, 1) + torch.arange(T, device=k8.device).view(1, T)).clamp(0, S - 1)
+    b = torch.arange(B, device=k8.device).view(B, 1)
+    for x, codes, scale in ((k, k8, k_scale), (v, v8, v_scale)):
+        c, s = kv_quantize_fp8(x)
+        codes[b, :, pos] = c.transpose(1, 2)
+        scale[b, :, pos] = s.transpose(1, 2)
+
+
 def flash_prefill(q, k, v, key_starts=None, start_pos: int = 0, scale: float = 1.0, tk=None,
                   alibi_slopes=None):
     """fp32 reference for the flash prefill kernel (masking semantics match
